@@ -10,8 +10,12 @@ gradient buffer per step.  Both launch forms work: under `python -m torch.distri
 (spawn_ranks: fresh children, before this process has touched the GPU).  The line carries `dist` = what the process group
 itself reported (backend, world size, an all-reduce head count); a run whose world size is not --gpus refuses to print.
 
-Prints ONE JSON line (rank 0).  Extra objects:
-  roofline     dominant kernel = gemm_f32_dma_kernel (exact-fp32 MFMA, LDS-DMA staged).  achieved = exact GEMM FLOPs
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and prints the headline (VP train
+trajectories/s, fp32, with `ms_per_step`); `--dump-outputs DIR` writes what the last timed step left to its caller (dump_outputs).
+Everything below runs only under `--full` (after the timed steps, same process):
+  dist.preflight  (N > 1) the self-diagnosis of the process group and the peer links, taken before the timed steps.
+  replica_param_spread  (N > 1) max - min over ranks of a parameter checksum after the timed steps.
+  roofline    dominant kernel = gemm_f32_dma_kernel (exact-fp32 MFMA, LDS-DMA staged).  achieved = exact GEMM FLOPs
                (sum 2MNK over launches; KV-cached decoder => this IS the algorithmic minimum of SURVEY
                8d up to the attention/elementwise terms) / summed launch duration from HIP event pairs attached to
                each dispatch on the launch stream (the kernel's own begin / end) in a separate instrumented leg of the same workload.
@@ -22,6 +26,8 @@ Prints ONE JSON line (rank 0).  Extra objects:
                with its own roofline object priced against the dense BF16 MFMA peak.  The fp32 line stays the headline.
   secondary    PPO env-steps/s (configs[2]) with its own roofline object (MFMA fraction on 11.5 MFLOP, HBM fraction on 29 KB per
                env-step, the dominant kernel's live launch timing, and the launch-latency floor of the cycle).
+  (N = 1)      tertiary (MPC expert), inference (VP sample + tile maps), small_batch, configs4, the PPO cycle on synthetic tables and
+               its data-parallel form at world 1 (secondary.dp_form).
 """
 import argparse
 import ctypes
@@ -56,6 +62,30 @@ def replica_spread(flat, world):
     dist.all_reduce(hi, op=dist.ReduceOp.MAX)
     dist.all_reduce(lo, op=dist.ReduceOp.MIN)
     return float((hi - lo).abs().max().item())
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, model, loss):
+    """What a caller of the timed step holds after the last timed step, one DIR/<name>.npy each: the loss it returned (float32 [1])
+    and the model state it updated -- the flat fp32 parameter buffer (every weight, after AdamW) and the DistillLayer BatchNorm running
+    statistics.  Inputs and every random draw of the step are seeded, so two builds given the same arguments can be compared file for file."""
+    import numpy as np
+    import torch
+    _, rm, rv, _ = model._engine_buffers()
+    arrays = {'loss': loss.detach().reshape(1), 'params': model._flat_p.detach(), 'bn_running_mean': rm.detach(), 'bn_running_var': rv.detach()}
+    torch.cuda.synchronize()
+    host = {}
+    for k, t in arrays.items():
+        a = t.cpu().numpy()
+        host[k] = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f'bench.py: the outputs hold {total} bytes, more than the {DUMP_LIMIT_BYTES} a dump may write')
+    os.makedirs(path, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(path, k + '.npy'), a)
 
 
 def synthetic_trajectories(B, S, T, seed=5):
@@ -451,13 +481,25 @@ def bench_vp_small(dev, steps=30, warmup=5):
 REAL_TABLES = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'tests', 'golden', 'env_tables_jin2022_4g.npz')
 
 
+def _real_tables_file():
+    """REAL_TABLES as one in-memory .npz.  The fixture is stored as REAL_TABLES + REAL_TABLES.part1, ... (no committed file is larger
+    than 1 MiB: tools/split_golden.py); the fixtures' own reader (tests/_golden.py) puts it back together."""
+    tests_dir = os.path.join(ROOT, 'tests')
+    sys.path.insert(0, tests_dir)
+    try:
+        import _golden
+    finally:
+        sys.path.remove(tests_dir)
+    return _golden.as_file(REAL_TABLES)
+
+
 def _ppo_tables(dev, kind, n_env_total):
     """'real': the reference's Jin2022 x 4G TRAIN split (18 videos x 45 users x 24 traces x 4 preferences = the 72-episode catalogue of
     generate_environment_samples, utils/common.py:60-84), packed by tools/gen_golden_tables_full.py out of the reference's own loaders --
     BASELINE configs[2] "Jin2022 tiles x 4G bandwidth traces".  'synthetic': same-shape random tables."""
     from mansy_immersivevideostreaming_amd.bitrate_selection.envs.mansy_env import EnvTables
     if kind == 'real':
-        return EnvTables.from_file(REAL_TABLES, 'train', dev, use_identifier=True)
+        return EnvTables.from_file(_real_tables_file(), 'train', dev, use_identifier=True)
     return EnvTables.synthetic(dev, seed=5, train_identifier_reward=True, n_sample=max(240, n_env_total))
 
 
@@ -709,7 +751,7 @@ def cpu_baseline_ppo(seconds=6.0):
     torch.set_num_threads(1)
     rs = np.random.RandomState(0)
     if os.path.exists(REAL_TABLES):       # the same tables as the GPU leg, host copy: the reference's Jin2022 x 4G train split
-        z = np.load(REAL_TABLES)
+        z = np.load(_real_tables_file())
         arrays = {k: z['train/' + k] for k in ('size', 'quality', 'video_len', 'vp_gt', 'vp_pred', 'vp_acc', 'vp_start', 'vp_end', 'trace_bw', 'trace_len', 'samples')}
         tables_desc = 'real Jin2022 x 4G train tables'
     else:
@@ -809,9 +851,17 @@ def main():
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--batch', type=int, default=4096, help='trajectories per GPU')
     ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline steps, run every other leg too (preflight, roofline, precision modes, PPO, CPU baselines, ...)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the loss and model state of the last timed step as DIR/<name>.npy (rank 0)')
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error('--gpus must be >= 1')
+    if args.steps < 1:
+        ap.error('--steps must be >= 1')
+    if args.warmup < 0:
+        ap.error('--warmup must be >= 0')
 
     # a fresh clone has no in-tree library (*.so is git-ignored): local rank 0 compiles it, the others wait for the file
     from mansy_immersivevideostreaming_amd import build_ext
@@ -859,8 +909,9 @@ def main():
             sys.exit(f'bench.py: asked for {args.gpus} ranks, the process group reports {dist_info}')
         # self-diagnosis before any timed leg: devices, peer-access matrix, hipIpc open of a fine-grained allocation from every
         # peer + one peer-memory average in both forms, the library all-reduce, each rank's core set -- gathered on every rank, printed by rank 0
-        dist_info['preflight'] = mdist.preflight(world, rank, dev, sizes=(1024, 435200))
-        dist_info['preflight']['pinned_cores_this_rank'] = host_cores
+        if args.full:
+            dist_info['preflight'] = mdist.preflight(world, rank, dev, sizes=(1024, 435200))
+            dist_info['preflight']['pinned_cores_this_rank'] = host_cores
 
     from mansy_immersivevideostreaming_amd.viewport_prediction.models import ViewportTransformerMTIO, FusedAdamW
     from mansy_immersivevideostreaming_amd._lib import lib, check
@@ -900,6 +951,23 @@ def main():
         dt = t.item()
     loss_val = float(loss.item())
     value = world * B * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, loss)
+    headline = {
+        'metric': 'viewport-trajectories/sec (VP train)', 'value': round(value, 1), 'unit': 'trajectories/s',
+        'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(dt / args.steps * 1e3, 3),
+        'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
+        'config': {'workload': f'VP Transformer train step (fwd+loss+bwd+AdamW), B={B}/GPU synthetic torus-walk '
+                               f'trajectories len 21 (hist 10 + cur 1 + pred 10), d=512, 8 heads, 2+2 layers, dropout on, '
+                               f'fp32 MFMA, decoder recurrence as two half-batches on two streams', 'two_stream': True, 'global_batch': B * world, 'parallelism': f'dp{world}'},
+        'final_loss': loss_val, 'dist': dist_info, 'full': args.full,
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # ---- roofline leg (rank 0): a HIP event pair on every GEMM dispatch of the same workload
     roof = None
@@ -975,18 +1043,13 @@ def main():
     ppo = bench_ppo(rank, world, dev, mdist, cycles=max(2, min(args.steps, 6)), warmup=3)      # warm-up: direct, capture + replay, replay
 
     if rank == 0:
-        out = {
-            'metric': 'viewport-trajectories/sec (VP train)', 'value': round(value, 1), 'unit': 'trajectories/s',
-            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(dt / args.steps * 1e3, 3),
-            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
-            'config': {'workload': f'VP Transformer train step (fwd+loss+bwd+AdamW), B={B}/GPU synthetic torus-walk '
-                                   f'trajectories len 21 (hist 10 + cur 1 + pred 10), d=512, 8 heads, 2+2 layers, dropout on, '
-                                   f'fp32 MFMA, decoder recurrence as two half-batches on two streams', 'two_stream': True, 'global_batch': B * world, 'parallelism': f'dp{world}'},
-            'final_loss': loss_val, 'replica_param_spread': vp_spread, 'dist': dist_info,
+        out = dict(headline)
+        out.update({
+            'replica_param_spread': vp_spread,
             'roofline': roof,
             'precision_modes': modes,
             'secondary': ppo,
-        }
+        })
         if world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline()
             out['secondary']['cpu_baseline'] = cpu_baseline_ppo()

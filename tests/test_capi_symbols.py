@@ -137,7 +137,8 @@ def test_bitrate_selection_host_mirrors_cpu(built):
     from mansy_immersivevideostreaming_amd.bitrate_selection.envs import expert_env
     from mansy_immersivevideostreaming_amd.bitrate_selection.models import mansy, simple_rl
     here = os.path.dirname(os.path.abspath(__file__))
-    Z = np.load(os.path.join(here, 'golden', 'a2c_reference.npz'))
+    import _golden
+    Z = _golden.load(os.path.join(here, 'golden', 'a2c_reference.npz'))
     keys = [str(k) for k in Z['net/keys']]
     table = mansy._Flat(2).table
     assert [n for n, _ in table] == [k for k in keys if not k.startswith('critic.feature_net.')]

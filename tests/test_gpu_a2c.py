@@ -7,6 +7,7 @@
 import os
 
 import numpy as np
+import _golden
 import pytest
 import torch
 
@@ -15,7 +16,7 @@ pytestmark = pytest.mark.gpu
 from oracle import a2c_oracle as ao  # noqa: E402
 from oracle import env as oenv  # noqa: E402
 
-Z = np.load(os.path.join(os.path.dirname(__file__), 'golden', 'a2c_reference.npz'))
+Z = _golden.load(os.path.join(os.path.dirname(__file__), 'golden', 'a2c_reference.npz'))
 FIELDS = ('size', 'quality', 'video_len', 'vp_gt', 'vp_pred', 'vp_acc', 'vp_start', 'vp_end', 'trace_bw', 'trace_len', 'samples')
 
 

@@ -12,6 +12,7 @@ import os
 import random
 
 import numpy as np
+import _golden
 import pytest
 import torch
 
@@ -23,7 +24,7 @@ from oracle import vp_oracle as vo  # noqa: E402
 HERE = os.path.dirname(__file__)
 GOLD = sorted(p for p in glob.glob(os.path.join(HERE, 'golden', 'vp_*.npz')) if 'vp_loop_' not in os.path.basename(p))
 IDS = [os.path.basename(p)[:-4] for p in GOLD]
-ZP = np.load(os.path.join(HERE, 'golden', 'ppo_reference.npz'))
+ZP = _golden.load(os.path.join(HERE, 'golden', 'ppo_reference.npz'))
 MODES = ['bf16x3', 'bf16x6']
 # max |C - C64| / max |C64| of one product on N(0,1) operands: fp32 accumulation ~1e-6; the bf16x3 variant drops the
 # a1*b1, a0*b2, a2*b0 terms (~3 * 2^-16 per element product, random signs)
@@ -248,7 +249,7 @@ def _build_vp(z, mode):
 @pytest.mark.parametrize('mode', MODES)
 @pytest.mark.parametrize('path', GOLD, ids=IDS)
 def test_vp_eval_and_sample_vs_reference_golden(K, path, mode):
-    z = np.load(path)
+    z = _golden.load(path)
     _, m = _build_vp(z, mode)
     m.eval()
     h, c = torch.from_numpy(z['history']).cuda(), torch.from_numpy(z['current']).cuda()
@@ -283,7 +284,7 @@ NORM_TOL = {'bf16x6': 1e-3, 'bf16x3': 2e-2}
 @pytest.mark.parametrize('branch', ['rep', 'mix'])
 @pytest.mark.parametrize('path', GOLD, ids=IDS)
 def test_vp_train_forward_backward_vs_reference_golden(K, path, branch, mode):
-    z = np.load(path)
+    z = _golden.load(path)
     mtio, m = _build_vp(z, mode)
     m.train()
     h, c, f = (torch.from_numpy(z[k]).cuda() for k in ('history', 'current', 'future'))

@@ -22,7 +22,7 @@ def test_bench_two_ranks_share_one_gpu_over_gloo():
         port = s.getsockname()[1]
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
            '--master-port', str(port), os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--no-cpu-baseline',
-           '--batch', '256']
+           '--batch', '256', '--full']
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
@@ -37,13 +37,23 @@ def test_bench_two_ranks_share_one_gpu_over_gloo():
 
 
 @pytest.mark.gpu
-def test_plain_bench_gpus_2_starts_two_ranks():
+def test_plain_bench_gpus_2_starts_two_ranks(tmp_path):
     """`python bench.py --gpus 2` with NO launcher around it (the driver's form for its scaling runs): bench.py itself starts
     the two rank processes; the line must say so -- n_gpus 2, the process group's own world size 2, an all-reduce head count
-    of 2 -- and the replicas must end bit-identical.  `--gpus 1` stays a single process with no process group."""
+    of 2 -- and the replicas must end bit-identical.  `--gpus 1` stays a single process with no process group.  The plain form prints the
+    headline only; with --full the same launch also carries the preflight, the replica spread and the PPO leg."""
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     env.update(MANSY_DIST_BACKEND='gloo', MANSY_SHARE_GPU='1', HSA_ENABLE_IPC_MODE_LEGACY='0')
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--batch', '256', '--no-cpu-baseline']
+    plain = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--batch', '256']
+    r = subprocess.run(plain, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
+    assert len(lines) == 1, r.stdout[-2000:]            # rank 0 only, relayed by the spawning parent
+    out = json.loads(lines[0])
+    assert out['n_gpus'] == 2 and out['config']['global_batch'] == 512 and out['steps'] == 2 and out['ms_per_step'] > 0 and out['full'] is False
+    assert {k: out['dist'][k] for k in ('backend', 'world_size', 'ranks_reporting', 'launcher')} == {'backend': 'gloo', 'world_size': 2, 'ranks_reporting': 2, 'launcher': 'self-spawn'}
+    assert 'roofline' not in out and 'secondary' not in out and 'preflight' not in out['dist'] and 0 < out['final_loss'] < 10
+    cmd = plain + ['--no-cpu-baseline', '--full']
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
@@ -61,11 +71,19 @@ def test_plain_bench_gpus_2_starts_two_ranks():
     if torch.cuda.device_count() < 2:
         r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
         assert r.returncode != 0 and '{"metric"' not in r.stdout and 'need 2 GPUs' in r.stderr
+    # the plain (headline-only) form, with the outputs of its last timed step written out
+    dump = tmp_path / 'dump'
     one = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1', '--batch', '256',
-                          '--no-cpu-baseline'], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+                          '--no-cpu-baseline', '--dump-outputs', str(dump)], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert one.returncode == 0, one.stdout[-2000:] + one.stderr[-4000:]
     o1 = json.loads([l for l in one.stdout.splitlines() if l.startswith('{"metric"')][0])
     assert o1['n_gpus'] == 1 and o1['dist']['world_size'] == 1 and o1['dist']['backend'] is None
+    assert o1['steps'] == 2 and o1['ms_per_step'] > 0 and o1['full'] is False and 'roofline' not in o1 and 'secondary' not in o1
+    loss, params = np.load(dump / 'loss.npy'), np.load(dump / 'params.npy')
+    assert loss.dtype == np.float32 and loss.shape == (1,) and float(loss[0]) == np.float32(o1['final_loss'])
+    assert params.dtype == np.float32 and params.size > 1_000_000 and np.isfinite(params).all()
+    for k in ('bn_running_mean', 'bn_running_var'):
+        assert np.isfinite(np.load(dump / (k + '.npy'))).all()
 
 
 @pytest.mark.gpu
@@ -157,7 +175,7 @@ def test_bench_two_ranks_with_the_peer_memory_allreduce():
     averaged gradients are bit-identical on both, so the replicas must end bit-identical like they do over the library collective."""
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     env.update(MANSY_DIST_BACKEND='gloo', MANSY_SHARE_GPU='1', HSA_ENABLE_IPC_MODE_LEGACY='0', MANSY_PEER_SYNC='1')
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--batch', '256', '--no-cpu-baseline']
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--batch', '256', '--no-cpu-baseline', '--full']
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith('{"metric"')][0])
@@ -179,7 +197,7 @@ def test_bench_chooses_its_gradient_average_by_probe_and_falls_back_together(cas
         env['MANSY_PEER_SYNC'] = '0'
     if case == 'one_rank_fails':
         env['MANSY_XG_TEST_FAIL_RANK'] = '1'
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--batch', '256', '--no-cpu-baseline']
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--batch', '256', '--no-cpu-baseline', '--full']
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     sec = json.loads([l for l in r.stdout.splitlines() if l.startswith('{"metric"')][0])['secondary']
@@ -203,7 +221,7 @@ def test_bench_eight_ranks_functional_on_the_shared_gpu():
     VP replicas identical."""
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     env.update(MANSY_DIST_BACKEND='gloo', MANSY_SHARE_GPU='1', HSA_ENABLE_IPC_MODE_LEGACY='0', MANSY_PEER_SYNC='slot')
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '8', '--steps', '1', '--warmup', '1', '--batch', '64', '--no-cpu-baseline']
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '8', '--steps', '1', '--warmup', '1', '--batch', '64', '--no-cpu-baseline', '--full']
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith('{"metric"')][0])

@@ -9,6 +9,7 @@ import ctypes
 import os
 
 import numpy as np
+import _golden
 import pytest
 import torch
 
@@ -16,7 +17,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle import ppo_oracle as po  # noqa: E402
 
-Z = np.load(os.path.join(os.path.dirname(__file__), 'golden', 'ppo_reference.npz'))
+Z = _golden.load(os.path.join(os.path.dirname(__file__), 'golden', 'ppo_reference.npz'))
 
 
 @pytest.fixture(scope='module')
@@ -362,7 +363,7 @@ def test_gae_kernel_reproduces_tianshou_published_known_answers(M):
     not installable here: the vectors are authentic to the best of the builder's knowledge, they were not generated by running tianshou): one
     environment (N = 1), each case alone and all four side by side as the columns of one padded [T][N] launch."""
     from mansy_immersivevideostreaming_amd._lib import check, lib, ptr, stream_ptr
-    KA = np.load(os.path.join(os.path.dirname(__file__), 'golden', 'tianshou_known_answers.npz'))
+    KA = _golden.load(os.path.join(os.path.dirname(__file__), 'golden', 'tianshou_known_answers.npz'))
     for i in range(int(KA['n_cases'])):
         rew, v_s, v_n, done = (KA[f'c{i}_{k}'] for k in ('rew', 'v_s', 'v_next', 'done'))
         T = len(rew)
@@ -690,7 +691,7 @@ def test_behavior_cloning_pretraining_vs_reference(M, tmp_path):
     import io
     import random
     from mansy_immersivevideostreaming_amd.bitrate_selection.utils.mansy_utils import behavior_cloning_pretraining
-    G = np.load(os.path.join(os.path.dirname(__file__), 'golden', 'bc_reference.npz'))
+    G = _golden.load(os.path.join(os.path.dirname(__file__), 'golden', 'bc_reference.npz'))
     sd = po.make_policy_state_dict(int(G['wseed']))
     pol = build_policy(M, sd, lr=float(G['lr']), ilr=float(G['ilr']), wd=float(G['wd']))
     nt, nv = int(G['n_train']), int(G['n_valid'])
@@ -964,7 +965,7 @@ def test_shipped_trained_checkpoint_vs_reference(M, mode):
     the imported reference: logits / values / identifier outputs within 1e-4, every argmax (bitrate) decision identical, the
     un-batched identifier reward -- in the exact-fp32 mode and in both split-bf16 modes."""
     from mansy_immersivevideostreaming_amd import kernels
-    G = np.load(os.path.join(os.path.dirname(__file__), 'golden', 'shipped_checkpoint_reference.npz'))
+    G = _golden.load(os.path.join(os.path.dirname(__file__), 'golden', 'shipped_checkpoint_reference.npz'))
     assert int(G['shared_feature_net_identical']) == 1
     uniq = {k[3:]: torch.from_numpy(G[k]) for k in G.files if k.startswith('w::')}
     sd = {}

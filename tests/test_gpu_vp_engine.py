@@ -10,6 +10,7 @@ import os
 import random
 
 import numpy as np
+import _golden
 import pytest
 import torch
 
@@ -46,7 +47,7 @@ def _build(MT, z, dropout_off=True):
 
 @pytest.mark.parametrize('path', GOLD, ids=IDS)
 def test_eval_forward_and_sample_vs_reference_golden(MT, path):
-    z = np.load(path)
+    z = _golden.load(path)
     m, sd = _build(MT, z)
     m.eval()
     h, c = torch.from_numpy(z['history']).cuda(), torch.from_numpy(z['current']).cuda()
@@ -65,7 +66,7 @@ def test_eval_forward_and_sample_vs_reference_golden(MT, path):
 @pytest.mark.parametrize('branch', ['rep', 'mix'])
 @pytest.mark.parametrize('path', GOLD, ids=IDS)
 def test_train_forward_backward_adamw_vs_reference_golden(MT, path, branch):
-    z = np.load(path)
+    z = _golden.load(path)
     m, sd = _build(MT, z)
     m.train()
     h, c, f = (torch.from_numpy(z[k]).cuda() for k in ('history', 'current', 'future'))
@@ -133,7 +134,7 @@ def test_every_intermediate_vs_oracle(MT, path, mode):
     (shared counter hash) at every site."""
     import ctypes
     from mansy_immersivevideostreaming_amd._lib import check, lib, ptr, stream_ptr
-    z = np.load(path)
+    z = _golden.load(path)
     m, sd = _build(MT, z, dropout_off=(mode != 'train_drop'))
     train = mode != 'eval'
     m.train(train)
@@ -175,7 +176,7 @@ def test_every_intermediate_vs_oracle(MT, path, mode):
 
 
 def test_dropout_statistics_and_determinism(MT):
-    z = np.load(GOLD[0])
+    z = _golden.load(GOLD[0])
     m, sd = _build(MT, z, dropout_off=False)
     m.train()
     h, c, f = (torch.from_numpy(z[k]).cuda() for k in ('history', 'current', 'future'))
@@ -202,7 +203,7 @@ def test_dropout_statistics_and_determinism(MT):
 
 def test_fused_train_step_equals_unfused(MT):
     """mansy_vp_train_step (one call) == zero_grad/forward/loss/backward/AdamW through the drop-in API."""
-    z = np.load([p for p in GOLD if 'vp_d64_' in p][0])
+    z = _golden.load([p for p in GOLD if 'vp_d64_' in p][0])
     h, c, f = (torch.from_numpy(z[k]).cuda() for k in ('history', 'current', 'future'))
     outs = []
     for fused in (False, True):
@@ -287,7 +288,7 @@ def test_bench_size_encoder_embedding_with_dropout(MT):
 def test_syncbn_hook_two_identical_ranks_equal_single(MT):
     """SyncBN plumbing: bn_sync_world=2 with an "all-reduce" that doubles the partial sums (= two ranks holding the same
     shard) must reproduce the single-rank loss, gradients and running statistics exactly where the math is scale-free."""
-    z = np.load(GOLD[2])
+    z = _golden.load(GOLD[2])
     h, c, f = (torch.from_numpy(z[k]).cuda() for k in ('history', 'current', 'future'))
     res = []
     for world in (1, 2):
@@ -398,7 +399,7 @@ def test_training_loop_vs_reference_capture(MT, path, fused):
     """four consecutive iterations of run_models.py:37-44 + the validation metric of :50-58 against a capture of the
     imported reference (tools/gen_golden_vp_loop.py): the MTIO repeat / shuffle decisions come out of the same host RNG stream,
     AdamW moments and BatchNorm running statistics evolve across the steps.  Both the one-call train_step and the module API."""
-    z = np.load(path)
+    z = _golden.load(path)
     m, _ = _build(MT, z)
     seed, lr = int(z['seed']), float(z['lr'])
     np.random.seed(seed); torch.manual_seed(seed); random.seed(seed)
@@ -462,7 +463,7 @@ def test_dropout_mask_policy_loss_curves(MT):
     tools/gen_golden_dropout_curves.py); the engine is trained the same way with 5 dropout seeds.  Per 40-step window the two
     seed-averaged curves must agree within 3 standard errors of the seed-to-seed spread (+ 5 % of the level): the mask policy
     moves the loss curve by less than changing the dropout seed does."""
-    z = np.load(os.path.join(os.path.dirname(__file__), 'golden', 'dropout_curves_vp_d64.npz'))
+    z = _golden.load(os.path.join(os.path.dirname(__file__), 'golden', 'dropout_curves_vp_d64.npz'))
     d, S, T, B, steps, nb = int(z['d']), int(z['S']), int(z['T']), int(z['B']), int(z['steps']), int(z['nb'])
     batches = [tuple(t.cuda() for t in vo.synthetic_trajectories(B, S, T, seed=int(z['batch_seed0']) + i)) for i in range(nb)]
     curves = []
@@ -492,7 +493,7 @@ def test_dropout_mask_policy_loss_curves_d512(MT):
     (tools/gen_golden_dropout_curves_d512.py).  The engine -- one mask per position instead of a fresh mask per recompute -- is
     trained the same way with 3 seeds of its own; per 20-step window the seed-averaged curves agree within 3 standard errors of the
     seed-to-seed spread + 5 % of the level, the start is the same and the loss falls as far."""
-    z = np.load(os.path.join(os.path.dirname(__file__), 'golden', 'dropout_curves_vp_d512.npz'))
+    z = _golden.load(os.path.join(os.path.dirname(__file__), 'golden', 'dropout_curves_vp_d512.npz'))
     d, T, steps, nb = int(z['d']), int(z['T']), int(z['steps']), int(z['nb'])
     batches = [tuple(torch.from_numpy(z[k][i]).cuda() for k in ('history', 'current', 'future')) for i in range(nb)]
     ref = z['curves']

@@ -1,7 +1,9 @@
 """CPU: the packed Jin2022 x 4G table fixture (tests/golden/env_tables_jin2022_4g.npz, written by tools/gen_golden_tables_full.py out of the
 reference's own loaders) against the build's host-side loader and catalogue logic, and the known answers the reference's shipped run holds
 for host logic: the minibatch split behind `save/gradient_step` = 18 and the catalogue walk behind the order of train_log.csv / valid_log.csv."""
+import glob
 import os
+import tarfile
 
 import numpy as np
 import pytest
@@ -46,12 +48,25 @@ def test_tree_written_from_the_fixture_loads_back_bit_identical(tree):
         assert np.array_equal(np.array(ids[3]), G[f'{sp}/ids_samples'])
 
 
-@pytest.mark.skipif(not os.path.exists('/root/reference/config.yml'), reason='build container only: reads the reference dataset tree')
-def test_loader_on_the_reference_tree_equals_the_reference_loaders():
+@pytest.fixture(scope='module')
+def reference_tree(tmp_path_factory):
+    """The reference's own dataset files for the three catalogues, byte for byte (tests/golden/jin2022_4g_reference_tree_*.tar.xz,
+    tools/gen_golden_reference_tree.py), unpacked in the reference's layout: config.yml next to datasets/ and bitrate_selection/."""
+    root = str(tmp_path_factory.mktemp('jin2022_reference'))
+    archives = sorted(glob.glob(os.path.join(os.path.dirname(__file__), 'golden', 'jin2022_4g_reference_tree_*.tar.xz')))
+    assert len(archives) == 3, archives
+    for a in archives:
+        with tarfile.open(a) as tar:
+            tar.extractall(root, filter='data')
+    os.makedirs(os.path.join(root, 'bitrate_selection'))
+    return root
+
+
+def test_loader_on_the_reference_tree_equals_the_reference_loaders(reference_tree):
     cwd = os.getcwd()
-    os.chdir('/root/reference/bitrate_selection')           # config.yml's directories are relative to the reference's scripts
+    os.chdir(os.path.join(reference_tree, 'bitrate_selection'))           # config.yml's directories are relative to the reference's scripts
     try:
-        config = get_config_from_yml('/root/reference/config.yml')
+        config = get_config_from_yml(os.path.join(reference_tree, 'config.yml'))
         for sp in jt.SPLITS:
             arrays, ids = EnvTables.arrays_from_dataset(config, 'Jin2022', '4G', sp, config.qoe_split['train'], seed=5)
             for k in EnvTables.FIELDS:

@@ -3,12 +3,13 @@
 (envs/simple_rl_env.py) reproduced from the MANSYEnv C oracle + the observation mapping -- bit-exact."""
 import os
 import numpy as np
+import _golden
 import pytest
 import torch
 from oracle import a2c_oracle as ao
 from oracle import env as oenv
 
-Z = np.load(os.path.join(os.path.dirname(__file__), 'golden', 'a2c_reference.npz'))
+Z = _golden.load(os.path.join(os.path.dirname(__file__), 'golden', 'a2c_reference.npz'))
 FIELDS = ('size', 'quality', 'video_len', 'vp_gt', 'vp_pred', 'vp_acc', 'vp_start', 'vp_end', 'trace_bw', 'trace_len', 'samples')
 
 

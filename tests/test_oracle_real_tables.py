@@ -4,6 +4,7 @@ tools/gen_golden_greedy_real.py): every decision, every reward bit for bit, the 
 import os
 
 import numpy as np
+import _golden
 import torch
 
 import _jin2022_tree as jt
@@ -15,8 +16,8 @@ HERE = os.path.dirname(__file__)
 
 def test_oracle_greedy_closed_loop_equals_imported_reference_on_real_tables():
     G = jt.load()
-    R = np.load(os.path.join(HERE, 'golden', 'greedy_real_reference.npz'))
-    W = np.load(os.path.join(HERE, 'golden', 'shipped_checkpoint_reference.npz'))
+    R = _golden.load(os.path.join(HERE, 'golden', 'greedy_real_reference.npz'))
+    W = _golden.load(os.path.join(HERE, 'golden', 'shipped_checkpoint_reference.npz'))
     uniq = {k[3:]: torch.from_numpy(W[k]) for k in W.files if k.startswith('w::')}
     sd = {k: uniq[k.replace('_actor_critic.', '').replace('critic.feature_net.', 'actor.feature_net.')] for k in po.make_policy_state_dict(0)}
     fields = ('size', 'quality', 'video_len', 'vp_gt', 'vp_pred', 'vp_acc', 'vp_start', 'vp_end', 'trace_bw', 'trace_len', 'samples')

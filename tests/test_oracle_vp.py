@@ -4,6 +4,7 @@ MTIO branches, loss, full gradients, BN running stats and one AdamW step."""
 import glob
 import os
 import numpy as np
+import _golden
 import pytest
 import torch
 
@@ -13,7 +14,7 @@ GOLD = sorted(p for p in glob.glob(os.path.join(os.path.dirname(__file__), 'gold
 
 
 def _load(path):
-    z = np.load(path, allow_pickle=False)
+    z = _golden.load(path, allow_pickle=False)
     sd = vo.make_state_dict(int(z['d']), int(z['wseed']), bias=bool(z['bias']))
     return z, sd
 
@@ -78,8 +79,16 @@ def test_train_forward_backward_adamw(path, branch):
         if key.startswith(f'train_{branch}_adamw::'):
             k = key.split('::')[1]
             p, g = params[k].detach(), params[k].grad
-            p1, _, _ = vo.adamw_step(p, g, torch.zeros_like(p), torch.zeros_like(p), step=1)
+            gref = torch.from_numpy(z[f'train_{branch}_grad::{k}'])
+            # the AdamW arithmetic on every element, from the reference's own gradient
+            p1, _, _ = vo.adamw_step(p, gref, torch.zeros_like(p), torch.zeros_like(p), step=1)
             np.testing.assert_allclose(p1.numpy(), z[key], atol=2e-7, rtol=1e-6, err_msg=k)
+            # from the oracle's gradient, on every element whose gradient the check above resolves: the first step moves a weight by
+            # lr * g / (|g| + eps), so below the gradient tolerance the step follows the rounding of the CPU's matmul kernels, not the model
+            p1, _, _ = vo.adamw_step(p, g, torch.zeros_like(p), torch.zeros_like(p), step=1)
+            live = np.abs(z[f'train_{branch}_grad::{k}']) > 1e-4 * np.abs(z[f'train_{branch}_grad::{k}']).max() + 1e-6
+            assert live.mean() > 0.5, (k, live.mean())
+            np.testing.assert_allclose(p1.numpy()[live], z[key][live], atol=2e-7, rtol=1e-6, err_msg=k)
 
 
 LOOPS = sorted(glob.glob(os.path.join(os.path.dirname(__file__), 'golden', 'vp_loop_*.npz')))
@@ -91,7 +100,7 @@ def test_training_loop_vs_reference_capture(path):
     of the imported reference (tools/gen_golden_vp_loop.py): MTIO decisions from the same host RNG stream (random.random(), then
     two np.random.shuffle per shuffled step -- mtio.py:77-87), AdamW moments and BatchNorm running statistics carried over."""
     import random
-    z = np.load(path)
+    z = _golden.load(path)
     d, T, B = int(z['d']), int(z['T']), int(z['B'])
     sd = vo.make_state_dict(d, int(z['wseed']), bias=bool(z['bias']))
     params = {k: v.clone().requires_grad_(True) for k, v in sd.items()
@@ -154,7 +163,7 @@ def test_linear_regression_baseline_vs_imported_reference(tag, T):
     """oracle.linear_regression_sample against the imported reference class (scikit-learn per trajectory; tools/gen_golden_linreg.py):
     bit-equal on the real Jin2022 windows; on the synthetic stress rows the closed form and LAPACK's least squares may differ in
     the last float64 bits, which survives the rounding to float32 for under 1 % of the values, by one ulp."""
-    z = np.load(os.path.join(os.path.dirname(__file__), 'golden', 'linreg_reference.npz'))
+    z = _golden.load(os.path.join(os.path.dirname(__file__), 'golden', 'linreg_reference.npz'))
     got = vo.linear_regression_sample(z[f'{tag}_history'], z[f'{tag}_current'], T)
     want = z[f'{tag}_pred']
     assert got.dtype == np.float32 and got.shape == want.shape

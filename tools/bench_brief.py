@@ -1,4 +1,4 @@
-"""One-line summary of a bench.py JSON line read from stdin:  python bench.py ... | python tools/bench_brief.py tag"""
+"""One-line summary of a bench.py JSON line read from stdin:  python bench.py --full ... | python tools/bench_brief.py tag"""
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print(sys.argv[1] if len(sys.argv) > 1 else '', d['value'], d['ms_per_step'], round(d['final_loss'], 6), d['roofline']['gemm_ms_per_step'],

@@ -20,12 +20,13 @@ from mansy_immersivevideostreaming_amd import kernels as K                      
 from mansy_immersivevideostreaming_amd.viewport_prediction.models import mtio               # noqa: E402
 from oracle import ppo_oracle as po                                                          # noqa: E402
 from oracle import vp_oracle as vo                                                           # noqa: E402
+import _golden                                                                               # noqa: E402
 
 MODES = ('f32', 'bf16x6', 'bf16x3')
 
 
 def vp_rows(path):
-    z = np.load(path)
+    z = _golden.load(path)
     d = int(z['d'])
     sd = vo.make_state_dict(d, int(z['wseed']), bias=bool(z['bias']))
     h, c, f = (torch.from_numpy(z[k]).cuda() for k in ('history', 'current', 'future'))
@@ -80,7 +81,7 @@ def ppo_rows():
         pass
     M = NS()
     M.mansy, M.ppo, M.env = mansy, mansy_ppo, mansy_env
-    Z = np.load(os.path.join(ROOT, 'tests', 'golden', 'ppo_reference.npz'))
+    Z = _golden.load(os.path.join(ROOT, 'tests', 'golden', 'ppo_reference.npz'))
     pol = build_policy(M, po.make_policy_state_dict(int(Z['wseed'])))
     obs = torch.from_numpy(Z['obs'][:64]).cuda()
     rows = []
