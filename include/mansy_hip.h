@@ -185,6 +185,25 @@ int mansy_env_step(const mansy_env_tables* T, void* state, int n_env, const int*
 int mansy_allocate_tile_rates(const float* pred_viewport, const int* actions, int n, const int video_rates[5], int* versions,
                               void* stream);
 
+/* ------------------------------------------------------------------ batched simulator (sessions stepped by per-tile rate choices)
+ * Simulator.simulate_download + QoEModel.calculate_qoe (bitrate_selection/simulators/simulator.py:88-108, utils/qoe.py:22-34) for n
+ * sessions, for callers that bring their own allocation instead of one of the 15 actions.  state: the records of mansy_env_state_bytes /
+ * mansy_env_init / mansy_env_reset, so sessions walk the same (seed + index_offset + i) % worker_num catalogue as environments do.  One
+ * state buffer belongs either to a vector environment (mansy_env_step, mansy_policy_*) or to a simulator, never both: the simulator does
+ * not maintain the observation's history rings.
+ * tile_rates int32 [n,64]: bitrate VERSION 0..4 per tile (values outside are clamped to [0,4]).  Outputs (any may be NULL except over):
+ * tile_size f32 [n,64], tile_quality f32 [n,64], actual_viewport u8 [n,64], scalars f64 [n,4] = chunk_size, chunk_quality, download_time,
+ * rebuffer_time, qoe_parts f32 [n,4] = qoe (unnormalised), qoe1, qoe2 (rebuffer), qoe3, over u8 [n].  auto_reset != 0: a session that
+ * ends opens the next catalogue entry (as the vector env does), and so does one that was already over when the call began.  A session
+ * that is already over (next_chunk > end_chunk, or never reset) and not auto-reset is skipped BEFORE any table load: zeros in every
+ * output, over = 1, state untouched. */
+int mansy_sim_download(const mansy_env_tables* T, void* state, int n, const int* tile_rates, float* tile_size, float* tile_quality,
+                       unsigned char* actual_viewport, double* scalars, float* qoe_parts, unsigned char* over, int auto_reset, void* stream);
+/* The getters of Simulator for n sessions: next_chunk i32 [n], buffer f64 [n], size f32 [n,5,64] and quality f32 [n,5,64] of the next
+ * chunk (raw, not normalised), gt / pred u8 [n,64], acc f64 [n].  Any output may be NULL.  Sessions that are over: zeros. */
+int mansy_sim_peek(const mansy_env_tables* T, const void* state, int n, int* next_chunk, double* buffer, float* size, float* quality,
+                   unsigned char* gt, unsigned char* pred, double* acc, void* stream);
+
 /* ------------------------------------------------------------------ MPC expert (demonstrations for behaviour cloning)
  * Replaces ExpertEnv._profile_viewport_qualities_sizes and ExpertEnv.choose_action (bitrate_selection/envs/
  * expert_env.py:126-181, 358-422) + ExpertSimulator.virtual_simulate_download_with_chunk_size /

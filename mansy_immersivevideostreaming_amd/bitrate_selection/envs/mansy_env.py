@@ -94,11 +94,30 @@ class EnvTables:
 
     # ---- builders ------------------------------------------------------------------------------
     @staticmethod
-    def arrays_from_dataset(config, dataset, network_dataset, mode, qoe_weights, seed=0, samples=None, lists=None):
+    def scale_traces(bw, trace_len, up, low):
+        """NetworkTrace(scale=(up, low)) (simulators/network.py:11-17) for a padded trace table: every trace is mapped linearly onto
+        [low, up] over its live bins, `low + (up - low) / (max - min) * (x - min)` in float64 with the reference's operation order.
+        Returns a new [n_trace, trace_len_max] float64 array (padding stays zero).  A constant trace, where the reference divides by
+        zero, raises MansyError."""
+        bw = np.asarray(bw, dtype=np.float64)
+        out = np.zeros_like(bw)
+        up, low = float(up), float(low)
+        for i, n in enumerate(np.asarray(trace_len).astype(np.int64)):
+            x = bw[i, :n]
+            max_, min_ = float(x.max()), float(x.min())
+            if max_ == min_:
+                raise MansyError(f'scale_traces: trace {i} is constant ({max_}), it cannot be mapped onto ({up}, {low})')
+            k = (up - low) / (max_ - min_)
+            out[i, :n] = low + k * (x - min_)
+        return out
+
+    @staticmethod
+    def arrays_from_dataset(config, dataset, network_dataset, mode, qoe_weights, seed=0, samples=None, lists=None, trace_scale=None):
         """Host half of `from_dataset`: reads the files Simulator.__init__ reads (simulator.py:30-45: prediction pickles, manifests,
         traces) for the episode catalogue MANSYEnv.__init__ enumerates (mansy_env.py:44-52) and returns (arrays, ids) -- numpy only, no
         device.  `samples`: explicit episode catalogue of (video, user, trace, qoe) list positions (ExpertEnv takes one);
-        `lists`: explicit (videos, users, traces) id lists instead of the split of `mode`."""
+        `lists`: explicit (videos, users, traces) id lists instead of the split of `mode`; `trace_scale`: (up, low) to rescale every
+        trace as NetworkTrace(scale=...) does (`scale_traces`)."""
         videos, users, traces = lists if lists is not None else (
             config.video_split[dataset][mode], config.user_split[dataset][mode], config.network_split[network_dataset][mode])
         if samples is not None:
@@ -146,6 +165,8 @@ class EnvTables:
         tl = np.zeros(len(trs), np.int32)
         for i, t in enumerate(trs):
             bw[i, :len(t)], tl[i] = t, len(t)
+        if trace_scale is not None:
+            bw = EnvTables.scale_traces(bw, tl, trace_scale[0], trace_scale[1])
         smp = np.array([(used_v.index(videos[a]), used_vp.index((videos[a], users[b])), used_t.index(traces[c]), d)
                         for a, b, c, d in samples], np.int32)
         # The device code indexes the viewport tables with `chunk - vp_start` and the manifest with `chunk`, unchecked; the
@@ -170,9 +191,10 @@ class EnvTables:
 
     @classmethod
     def from_dataset(cls, config, dataset, network_dataset, mode, qoe_weights, device, seed=0, use_identifier=False, samples=None,
-                     lists=None):
+                     lists=None, trace_scale=None):
         """The tables of one split read from the dataset tree (`arrays_from_dataset`), uploaded."""
-        arrays, ids = cls.arrays_from_dataset(config, dataset, network_dataset, mode, qoe_weights, seed=seed, samples=samples, lists=lists)
+        arrays, ids = cls.arrays_from_dataset(config, dataset, network_dataset, mode, qoe_weights, seed=seed, samples=samples, lists=lists,
+                                              trace_scale=trace_scale)
         return cls(arrays, qoe_weights, device, video_rates=config.video_rates, startup_download=config.startup_download,
                    chunk_length=config.chunk_length, max_size=config.max_size, max_throughput=config.max_throughput,
                    train_identifier_reward=(mode == 'train' and use_identifier), ids=ids)

@@ -1,0 +1,201 @@
+"""Device counterpart of bitrate_selection/simulators/simulator.py:9-114 (+ network.py, buffer.py, hmdtrace.py and utils/qoe.py below
+it) for callers that bring their OWN per-tile rate allocation: a rule-based ABR, another action space, a per-tile optimiser, an upper
+bound that allocates on the ground-truth viewport.
+
+* `BatchedSimulator` -- n sessions of the `EnvTables` episode catalogue stepped by ONE kernel launch (csrc/sim.hip): tile versions in,
+                        tile sizes / qualities / viewport / download + rebuffer time / QoE terms / over flags out, all device tensors.
+* `Simulator`        -- one session with the reference's constructor and method names (numpy / Python values in and out).
+
+The session records are the environment's (`mansy_env_init` / `mansy_env_reset`), so sessions walk the catalogue exactly as the
+environments of `MANSYVecEnv` do.  A state buffer belongs either to a `MANSYVecEnv` or to a simulator, never both: the simulator keeps no
+action history, so the observation rings of such a record are not maintained."""
+import ctypes
+import types
+
+import numpy as np
+import torch
+
+from ..._lib import MansyError, check, lib, ptr, stream_ptr
+from ..envs.mansy_env import OBS_LD, EnvTables
+
+N_TILE, N_RATE = 64, 5
+
+
+class BatchedSimulator:
+    """n sessions; session i (global index `index_offset + i` of `worker_num`) opens catalogue entry (seed + index_offset + i) %
+    worker_num first and strides by worker_num on every reset, like environment i of `MANSYVecEnv`.  The returned tensors are this
+    object's buffers, overwritten by the next call."""
+
+    def __init__(self, tables, n, seed=0, index_offset=0, worker_num=None):
+        self.device = torch.device(tables.device)
+        if self.device.type != 'cuda':
+            raise MansyError('BatchedSimulator runs on the device: tables on a cuda (ROCm) device are required, there is no CPU path')
+        self.tables, self.n = tables, int(n)
+        if self.n < 1:
+            raise MansyError('BatchedSimulator: n must be >= 1')
+        self.worker_num = int(worker_num) if worker_num is not None else self.n
+        L = lib()
+        self.state = torch.zeros(self.n * L.mansy_env_state_bytes(), dtype=torch.uint8, device=self.device)
+        check(L.mansy_env_init(ptr(self.state), self.n, int(index_offset), self.worker_num, int(seed), stream_ptr(self.device)), 'mansy_env_init')
+        self._worker = (int(seed) + int(index_offset) + np.arange(self.n, dtype=np.int64)) % self.worker_num      # host mirror of worker_id
+        dev = self.device
+        f32, f64, u8 = (dict(dtype=t, device=dev) for t in (torch.float32, torch.float64, torch.uint8))
+        self.tile_size = torch.zeros(self.n, N_TILE, **f32)
+        self.tile_quality = torch.zeros(self.n, N_TILE, **f32)
+        self.actual_viewport = torch.zeros(self.n, N_TILE, **u8)
+        self.scalars = torch.zeros(self.n, 4, **f64)          # chunk_size, chunk_quality, download_time, rebuffer_time
+        self.qoe_parts = torch.zeros(self.n, 4, **f32)        # qoe (unnormalised), qoe1, qoe2 (rebuffer), qoe3
+        self.over = torch.ones(self.n, **u8)
+        self._peek = dict(next_chunk=torch.zeros(self.n, dtype=torch.int32, device=dev), buffer=torch.zeros(self.n, **f64),
+                          size=torch.zeros(self.n, N_RATE, N_TILE, **f32), quality=torch.zeros(self.n, N_RATE, N_TILE, **f32),
+                          gt=torch.zeros(self.n, N_TILE, **u8), pred=torch.zeros(self.n, N_TILE, **u8), acc=torch.zeros(self.n, **f64))
+        self._out = types.SimpleNamespace(
+            tile_size=self.tile_size, tile_quality=self.tile_quality, actual_viewport=self.actual_viewport, scalars=self.scalars,
+            chunk_size=self.scalars[:, 0], chunk_quality=self.scalars[:, 1], download_time=self.scalars[:, 2], rebuffer_time=self.scalars[:, 3],
+            qoe_parts=self.qoe_parts, qoe=self.qoe_parts[:, 0], qoe1=self.qoe_parts[:, 1], qoe2=self.qoe_parts[:, 2], qoe3=self.qoe_parts[:, 3],
+            over=self.over)
+
+    def reset(self):
+        """Every session opens its next catalogue entry at chunk startup_download + 1 with an empty clock (MANSYEnv.reset's
+        `Simulator(...)` + `QoEModel(...)`, mansy_env.py:100-115)."""
+        n_sample = self.tables.n_sample
+        sample = self._worker % n_sample
+        bad = sorted(set(int(s) for s in sample) & set(getattr(self.tables, 'unvisitable', ())))
+        if bad:
+            raise MansyError(f'BatchedSimulator.reset: catalogue entries {bad[:8]} hold no tables (negative slots in `samples`)')
+        self._worker = (self._worker + self.worker_num) % n_sample
+        obs = torch.empty(self.n, OBS_LD, dtype=torch.float32, device=self.device)     # mansy_env_reset writes an observation: dropped
+        check(lib().mansy_env_reset(ctypes.byref(self.tables.c), ptr(self.state), self.n, ptr(obs), stream_ptr(self.device)), 'mansy_env_reset')
+        return self
+
+    def peek(self):
+        """The getters of Simulator for all sessions, as a dict of device tensors: next_chunk i32 [n], buffer f64 [n], size / quality
+        f32 [n,5,64] of the next chunk (raw), gt / pred u8 [n,64], acc f64 [n].  Sessions that are over show zeros."""
+        p = self._peek
+        check(lib().mansy_sim_peek(ctypes.byref(self.tables.c), ptr(self.state), self.n, ptr(p['next_chunk']), ptr(p['buffer']), ptr(p['size']),
+                                   ptr(p['quality']), ptr(p['gt']), ptr(p['pred']), ptr(p['acc']), stream_ptr(self.device)), 'mansy_sim_peek')
+        return p
+
+    def simulate_download(self, tile_rates, auto_reset=False, validate=False):
+        """tile_rates: int32 cuda tensor [n,64], bitrate VERSION 0..4 per tile (values outside are clamped by the kernel; validate=True
+        raises instead, at the cost of one synchronisation).  Returns a namespace of device tensors: tile_size, tile_quality [n,64] f32,
+        actual_viewport [n,64] u8, chunk_size, chunk_quality, download_time, rebuffer_time [n] f64 (columns of `scalars` [n,4]),
+        qoe, qoe1, qoe2, qoe3 [n] f32 (columns of `qoe_parts` [n,4]; qoe is the unnormalised one), over [n] u8.  auto_reset: a session
+        that ends opens its next catalogue entry, as the vector environment does; without it a finished session returns zeros and
+        over = 1 until `reset()`."""
+        if not isinstance(tile_rates, torch.Tensor) or not tile_rates.is_cuda or tile_rates.dtype != torch.int32:
+            raise MansyError('tile_rates must be an int32 cuda tensor (there is no CPU path)')
+        if tuple(tile_rates.shape) != (self.n, N_TILE) or not tile_rates.is_contiguous() or tile_rates.device != self.state.device:
+            raise MansyError(f'tile_rates must be a contiguous [{self.n}, {N_TILE}] tensor on {self.state.device}')
+        if validate and bool(((tile_rates < 0) | (tile_rates > N_RATE - 1)).any().item()):
+            raise MansyError(f'tile_rates holds a version outside 0..{N_RATE - 1}')
+        if auto_reset and getattr(self.tables, 'unvisitable', None):
+            raise MansyError('auto_reset walks the whole catalogue, but some of its entries hold no tables (negative slots in `samples`)')
+        check(lib().mansy_sim_download(ctypes.byref(self.tables.c), ptr(self.state), self.n, ptr(tile_rates), ptr(self.tile_size),
+                                       ptr(self.tile_quality), ptr(self.actual_viewport), ptr(self.scalars), ptr(self.qoe_parts),
+                                       ptr(self.over), int(bool(auto_reset)), stream_ptr(self.device)), 'mansy_sim_download')
+        return self._out
+
+
+class Simulator:
+    """Drop-in single session (reference constructor signature, simulator.py:15): the viewport trace of (video, user), the network trace
+    `trace` and the manifest of `video`, downloaded chunk by chunk with the caller's tile rates.  Values come back as the reference's
+    types (float32 arrays, Python numbers); each call is one launch and one small copy to the host -- use `BatchedSimulator` for
+    throughput.  There is no CPU path: device='cpu' raises MansyError."""
+
+    def __init__(self, config, dataset, video, user, network_dataset, trace, startup_download, trace_scale=None, device='cuda'):
+        if torch.device(device).type != 'cuda':
+            raise MansyError('Simulator runs on the device: a cuda (ROCm) device is required, there is no CPU path')
+        self.config = config
+        self.startup_download = int(startup_download)
+        arrays, ids = EnvTables.arrays_from_dataset(config, dataset, network_dataset, None, [(1, 1, 1)], samples=[(0, 0, 0, 0)],
+                                                    lists=([video], [user], [trace]), trace_scale=trace_scale)
+        self.video_length = int(arrays['video_len'][0])
+        self.start_chunk = int(arrays['vp_start'][0])
+        self.end_chunk = min(int(arrays['vp_end'][0]), self.video_length - 1)
+        self.chunk_num = self.end_chunk - self.start_chunk + 1
+        if self.startup_download + 1 < self.start_chunk:                       # simulator.py:45
+            raise MansyError(f'the viewport trace starts at chunk {self.start_chunk}, after startup_download + 1 = {self.startup_download + 1}')
+        self.tables = EnvTables(arrays, [(1, 1, 1)], device, video_rates=config.video_rates, startup_download=self.startup_download,
+                                chunk_length=config.chunk_length, max_size=config.max_size, max_throughput=config.max_throughput, ids=ids)
+        self.device = self.tables.device
+        self._sim = BatchedSimulator(self.tables, 1, seed=0, index_offset=0, worker_num=1)
+        self._rates = torch.zeros(1, N_TILE, dtype=torch.int32, device=self.device)
+        self.reset()
+
+    # ---- getters (simulator.py:48-86); chunk=None is the next chunk, read from the device
+    def _peek(self):
+        if self.next_chunk > self.end_chunk:
+            raise MansyError(f'the session is over (next chunk {self.next_chunk} > end chunk {self.end_chunk})')
+        return self._sim.peek()
+
+    def get_next_chunk_size(self, chunk=None):
+        if chunk is None:
+            return self._peek()['size'][0].cpu().numpy()
+        return self.tables.host['size'][0, int(chunk)].astype(np.float32)
+
+    def get_chunk_num(self):
+        return self.chunk_num
+
+    def get_next_chunk_quality(self, chunk=None):
+        if chunk is None:
+            return self._peek()['quality'][0].cpu().numpy()
+        return self.tables.host['quality'][0, int(chunk)].astype(np.float32)
+
+    def get_next_chunk_info(self, chunk=None):
+        chunk = self.next_chunk if chunk is None else int(chunk)
+        return self.tables.host['size'][0, chunk].tolist(), self.tables.host['quality'][0, chunk].tolist()
+
+    def get_viewport(self, chunk=None, flatten=True):
+        if chunk is None:
+            p = self._peek()
+            gt, pred, acc = p['gt'][0].cpu().numpy(), p['pred'][0].cpu().numpy(), np.float64(p['acc'][0].item())
+        else:
+            j = int(chunk) - self.start_chunk
+            if j < 0:
+                raise MansyError(f'chunk {chunk} lies before the viewport trace (it starts at chunk {self.start_chunk})')
+            h = self.tables.host
+            gt, pred, acc = h['vp_gt'][0, j], h['vp_pred'][0, j], np.float64(h['vp_acc'][0, j])
+        gt, pred = np.array(gt, dtype=np.float32), np.array(pred, dtype=np.float32)
+        if not flatten:
+            gt = gt.reshape(self.config.tile_num_height, self.config.tile_num_width)
+            pred = pred.reshape(self.config.tile_num_height, self.config.tile_num_width)
+        return gt, pred, acc
+
+    def get_buffer_size(self):
+        if self.next_chunk > self.end_chunk:                   # the device shows zeros for a finished session: the host copy serves it
+            return self._buffer
+        return float(self._sim.peek()['buffer'][0].item())
+
+    def get_next_chunk(self):
+        return self.next_chunk
+
+    def simulate_download(self, tile_rates):
+        """Given the bitrate version of each tile, download the next chunk (simulator.py:88-108).  Returns the reference's 8-tuple:
+        tile sizes, tile qualities (float32 [64]), chunk_size (int), chunk_quality (float; the reference's is an int where the manifest
+        stores integers), download_time, rebuffer_time (float), actual_viewport (uint8 [64]), over (bool)."""
+        if self.next_chunk > self.end_chunk:
+            raise MansyError(f'the session is over (next chunk {self.next_chunk} > end chunk {self.end_chunk})')
+        rates = np.asarray(tile_rates).reshape(-1)
+        if rates.size != N_TILE or (rates < 0).any() or (rates > N_RATE - 1).any():
+            raise MansyError(f'tile_rates must hold {N_TILE} versions in 0..{N_RATE - 1}')
+        self._rates.copy_(torch.from_numpy(rates.astype(np.int32)).view(1, N_TILE))
+        out = self._sim.simulate_download(self._rates)
+        sc = out.scalars[0].cpu().numpy()
+        download_time, rebuffer_time = float(sc[2]), float(sc[3])
+        # PlaybackBuffer.push_chunk (buffer.py:8-15) on the host copy that get_buffer_size() serves after the last chunk too
+        chunk_length = self.config.chunk_length
+        self._buffer = chunk_length if download_time > self._buffer else self._buffer - download_time + chunk_length
+        self.next_chunk += 1
+        over = bool(out.over[0].item())
+        assert over == (self.next_chunk > self.end_chunk)
+        return (out.tile_size[0].cpu().numpy(), out.tile_quality[0].cpu().numpy(), int(sc[0]), float(sc[1]), download_time, rebuffer_time,
+                out.actual_viewport[0].cpu().numpy(), over)
+
+    def reset(self):
+        """Restarts the SAME session at chunk startup_download + 1 with an empty clock and the start-up buffer, as a freshly constructed
+        reference Simulator would.  (The reference's own reset(), simulator.py:110-114, sets next_chunk = startup_download -- one chunk
+        earlier than its constructor does; its environment never relies on it, it builds a new Simulator per episode.)"""
+        self._sim.reset()                      # a one-entry catalogue: the next entry is this session again
+        self.next_chunk = self.startup_download + 1
+        self._buffer = self.config.chunk_length * 3
