@@ -204,6 +204,33 @@ int mansy_sim_download(const mansy_env_tables* T, void* state, int n, const int*
 int mansy_sim_peek(const mansy_env_tables* T, const void* state, int n, int* next_chunk, double* buffer, float* size, float* quality,
                    unsigned char* gt, unsigned char* pred, double* acc, void* stream);
 
+/* ------------------------------------------------------------------ batched simulator: what-if (read-only look-ahead over candidate plans)
+ * The planner's pattern of ExpertEnv.choose_action (bitrate_selection/envs/expert_env.py:358-422: download candidate plans virtually
+ * over a horizon with the real trace, score them on the ground-truth viewport, leave the simulator where it was) for plans made of
+ * ARBITRARY tile versions.  A virtual step is Simulator.simulate_download (simulators/simulator.py:88-108) on NetworkTrace.simulate_download
+ * (simulators/network.py:22-35) and PlaybackBuffer.push_chunk (simulators/buffer.py:8-15), scored by QoEModel.calculate_qoe
+ * (utils/qoe.py:22-34) -- mansy_sim_download's arithmetic, so a virtual step returns the bits the committed step would.  `state` is only
+ * read: no byte of it changes.
+ * plans int32 [n,K,H,64]: candidate k of session i downloads chunks next_chunk, next_chunk + 1, .. with the VERSIONS plans[i,k,t,:]
+ * (values outside are clamped to [0,4]); the previous viewport quality is carried from step to step inside the candidate.
+ * steps i32 [n] = min(H, end_chunk - next_chunk + 1), 0 for a session that is over or was never reset; a look-ahead never crosses an
+ * episode boundary.  qoe_parts f32 [n,K,H,4] = qoe (unnormalised), qoe1, qoe2 (rebuffer), qoe3 and scalars f64 [n,K,H,4] = chunk_size,
+ * chunk_quality, download_time, rebuffer_time of every virtual step (both nullable; rows t >= steps[i] are zeros).  total f32 [n,K] =
+ * ((0 + qoe_0) + qoe_1) + .. over t < steps[i] in float32.  best i32 [n] / best_total f32 [n] (nullable): the FIRST candidate with the
+ * strictly largest total (-0.0 == 0.0, a NaN total never wins) and its total; candidate 0 where every total is NaN or steps[i] == 0.
+ * MANSY_SIM_MAX_HORIZON: deeper than the expert's deepest search (MANSY_EXPERT_MAX_HORIZON).
+ * MANSY_SIM_MAX_CANDIDATES: 4096 holds every three-step plan of the 15 actions (3375) and keeps the scan for the best candidate of one
+ * session a single wavefront's work (at most 64 strided reads per lane).  n * K must stay below 2^31 (one wavefront per candidate). */
+#define MANSY_SIM_MAX_HORIZON 8
+#define MANSY_SIM_MAX_CANDIDATES 4096
+int mansy_sim_lookahead(const mansy_env_tables* T, const void* state, int n, const int* plans, int K, int H, float* qoe_parts,
+                        double* scalars, float* total, int* steps, int* best, float* best_total, void* stream);
+/* mansy_sim_peek's table getters for chunk next_chunk + ahead, 0 <= ahead < MANSY_SIM_MAX_HORIZON: size / quality f32 [n,5,64], gt / pred
+ * u8 [n,64], acc f64 [n] (all nullable), valid u8 [n] = 1 iff the session is open and next_chunk + ahead <= end_chunk.  A row that is not
+ * valid is zeros, written without touching a table. */
+int mansy_sim_peek_ahead(const mansy_env_tables* T, const void* state, int n, int ahead, float* size, float* quality, unsigned char* gt,
+                         unsigned char* pred, double* acc, unsigned char* valid, void* stream);
+
 /* ------------------------------------------------------------------ MPC expert (demonstrations for behaviour cloning)
  * Replaces ExpertEnv._profile_viewport_qualities_sizes and ExpertEnv.choose_action (bitrate_selection/envs/
  * expert_env.py:126-181, 358-422) + ExpertSimulator.virtual_simulate_download_with_chunk_size /

@@ -111,6 +111,8 @@ _PROTOS = {
     'mansy_allocate_tile_rates': [P, P, c_int, P, P, P],
     'mansy_sim_download': [P, P, c_int, P, P, P, P, P, P, P, c_int, P],
     'mansy_sim_peek': [P, P, c_int, P, P, P, P, P, P, P, P],
+    'mansy_sim_lookahead': [P, P, c_int, P, c_int, c_int, P, P, P, P, P, P, P],
+    'mansy_sim_peek_ahead': [P, P, c_int, c_int, P, P, P, P, P, P, P],
     'mansy_expert_profile': [P, P, c_int, P, P, P, P, P, P, P],
     'mansy_expert_choose_action': [P, P, c_int, c_int, P, P, P, P, P, P, P, P],
     'mansy_net_num_params': [c_int],

@@ -6,6 +6,11 @@ bound that allocates on the ground-truth viewport.
                         tile sizes / qualities / viewport / download + rebuffer time / QoE terms / over flags out, all device tensors.
 * `Simulator`        -- one session with the reference's constructor and method names (numpy / Python values in and out).
 
+Both also answer "what would happen if" without moving a session: `lookahead(plans)` downloads K candidate plans of H chunks virtually
+from where every session stands (one launch, the state buffer is only read) and `peek(ahead=t)` shows the table rows of the chunks such
+plans are made for -- the pattern of the reference's own planner (ExpertEnv.choose_action, envs/expert_env.py:358-422) for arbitrary tile
+versions.
+
 The session records are the environment's (`mansy_env_init` / `mansy_env_reset`), so sessions walk the catalogue exactly as the
 environments of `MANSYVecEnv` do.  A state buffer belongs either to a `MANSYVecEnv` or to a simulator, never both: the simulator keeps no
 action history, so the observation rings of such a record are not maintained."""
@@ -19,6 +24,7 @@ from ..._lib import MansyError, check, lib, ptr, stream_ptr
 from ..envs.mansy_env import OBS_LD, EnvTables
 
 N_TILE, N_RATE = 64, 5
+MAX_HORIZON, MAX_CANDIDATES = 8, 4096          # MANSY_SIM_MAX_HORIZON, MANSY_SIM_MAX_CANDIDATES of include/mansy_hip.h
 
 
 class BatchedSimulator:
@@ -54,6 +60,8 @@ class BatchedSimulator:
             chunk_size=self.scalars[:, 0], chunk_quality=self.scalars[:, 1], download_time=self.scalars[:, 2], rebuffer_time=self.scalars[:, 3],
             qoe_parts=self.qoe_parts, qoe=self.qoe_parts[:, 0], qoe1=self.qoe_parts[:, 1], qoe2=self.qoe_parts[:, 2], qoe3=self.qoe_parts[:, 3],
             over=self.over)
+        self._peek_ahead = None               # peek(ahead > 0) has buffers of its own, made on first use
+        self._look = {}                       # (K, H) -> lookahead()'s buffers and the two namespaces over them
 
     def reset(self):
         """Every session opens its next catalogue entry at chunk startup_download + 1 with an empty clock (MANSYEnv.reset's
@@ -68,13 +76,75 @@ class BatchedSimulator:
         check(lib().mansy_env_reset(ctypes.byref(self.tables.c), ptr(self.state), self.n, ptr(obs), stream_ptr(self.device)), 'mansy_env_reset')
         return self
 
-    def peek(self):
+    def peek(self, ahead=0):
         """The getters of Simulator for all sessions, as a dict of device tensors: next_chunk i32 [n], buffer f64 [n], size / quality
-        f32 [n,5,64] of the next chunk (raw), gt / pred u8 [n,64], acc f64 [n].  Sessions that are over show zeros."""
+        f32 [n,5,64] of the next chunk (raw), gt / pred u8 [n,64], acc f64 [n].  Sessions that are over show zeros.
+        ahead > 0 (below MAX_HORIZON): the table getters for chunk next_chunk + ahead instead, for a caller that plans over future chunks:
+        size, quality, gt, pred, acc and valid u8 [n] (1 iff the session is open and that chunk is one of its own; other rows are
+        zeros), in buffers of their own that the next peek(ahead > 0) overwrites."""
+        if isinstance(ahead, bool) or not isinstance(ahead, (int, np.integer)) or not 0 <= ahead < MAX_HORIZON:
+            raise MansyError(f'ahead must be an integer in 0..{MAX_HORIZON - 1}')
+        if ahead > 0:
+            if self._peek_ahead is None:
+                dev = self.device
+                self._peek_ahead = dict(
+                    size=torch.zeros(self.n, N_RATE, N_TILE, dtype=torch.float32, device=dev),
+                    quality=torch.zeros(self.n, N_RATE, N_TILE, dtype=torch.float32, device=dev),
+                    gt=torch.zeros(self.n, N_TILE, dtype=torch.uint8, device=dev), pred=torch.zeros(self.n, N_TILE, dtype=torch.uint8, device=dev),
+                    acc=torch.zeros(self.n, dtype=torch.float64, device=dev), valid=torch.zeros(self.n, dtype=torch.uint8, device=dev))
+            p = self._peek_ahead
+            check(lib().mansy_sim_peek_ahead(ctypes.byref(self.tables.c), ptr(self.state), self.n, int(ahead), ptr(p['size']), ptr(p['quality']),
+                                             ptr(p['gt']), ptr(p['pred']), ptr(p['acc']), ptr(p['valid']), stream_ptr(self.device)),
+                  'mansy_sim_peek_ahead')
+            return p
         p = self._peek
         check(lib().mansy_sim_peek(ctypes.byref(self.tables.c), ptr(self.state), self.n, ptr(p['next_chunk']), ptr(p['buffer']), ptr(p['size']),
                                    ptr(p['quality']), ptr(p['gt']), ptr(p['pred']), ptr(p['acc']), stream_ptr(self.device)), 'mansy_sim_peek')
         return p
+
+    def lookahead(self, plans, per_step=True):
+        """What would happen if: K candidate plans per session downloaded VIRTUALLY over H chunks from where the session stands, with
+        the real trace and the ground-truth viewport (the pattern of ExpertEnv.choose_action, expert_env.py:358-422, for arbitrary tile
+        versions).  The sessions do not move: the state buffer is only read.
+        plans: int32 cuda tensor [n,K,H,64], contiguous; plans[i,k,t] holds the bitrate VERSION 0..4 of every tile of chunk next_chunk + t
+        (values outside are clamped by the kernel), 1 <= K <= MAX_CANDIDATES, 1 <= H <= MAX_HORIZON.
+        Returns a namespace of device tensors, without a synchronisation: total f32 [n,K] (float32 sum of the steps' qoe in step order),
+        steps i32 [n] = min(H, chunks the session has left; 0 when it is over), best i32 [n] (first candidate with the strictly largest
+        total; a NaN never wins) and best_total f32 [n].  per_step adds qoe_parts f32 [n,K,H,4] with the views qoe, qoe1, qoe2, qoe3 and
+        scalars f64 [n,K,H,4] with the views chunk_size, chunk_quality, download_time, rebuffer_time; rows t >= steps[i] are zeros.
+        The buffers are cached per (K, H) and overwritten by the next call with that shape."""
+        if not isinstance(plans, torch.Tensor) or plans.dtype != torch.int32:
+            raise MansyError('plans must be an int32 cuda tensor (there is no CPU path)')
+        if plans.dim() != 4 or plans.shape[0] != self.n or plans.shape[3] != N_TILE:
+            raise MansyError(f'plans must have the shape [{self.n}, K, H, {N_TILE}], not {list(plans.shape)}')
+        K, H = int(plans.shape[1]), int(plans.shape[2])
+        if not 1 <= K <= MAX_CANDIDATES:
+            raise MansyError(f'plans holds K = {K} candidates per session: 1..{MAX_CANDIDATES} are supported')
+        if not 1 <= H <= MAX_HORIZON:
+            raise MansyError(f'plans holds H = {H} steps per candidate: 1..{MAX_HORIZON} are supported')
+        if self.n * K >= 2 ** 31:
+            raise MansyError('n * K must stay below 2^31')
+        if not plans.is_cuda or plans.device != self.state.device or not plans.is_contiguous():
+            raise MansyError(f'plans must be a contiguous int32 cuda tensor on {self.state.device} (there is no CPU path)')
+        b = self._look.get((K, H))
+        if b is None:
+            dev = self.device
+            b = types.SimpleNamespace(total=torch.zeros(self.n, K, dtype=torch.float32, device=dev), steps=torch.zeros(self.n, dtype=torch.int32, device=dev),
+                                      best=torch.zeros(self.n, dtype=torch.int32, device=dev), best_total=torch.zeros(self.n, dtype=torch.float32, device=dev),
+                                      qoe_parts=None, scalars=None, short=None, full=None)
+            b.short = types.SimpleNamespace(total=b.total, steps=b.steps, best=b.best, best_total=b.best_total)
+            self._look[(K, H)] = b
+        if per_step and b.full is None:
+            b.qoe_parts = torch.zeros(self.n, K, H, 4, dtype=torch.float32, device=self.device)
+            b.scalars = torch.zeros(self.n, K, H, 4, dtype=torch.float64, device=self.device)
+            q, s = b.qoe_parts, b.scalars
+            b.full = types.SimpleNamespace(total=b.total, steps=b.steps, best=b.best, best_total=b.best_total, qoe_parts=q, qoe=q[..., 0],
+                                           qoe1=q[..., 1], qoe2=q[..., 2], qoe3=q[..., 3], scalars=s, chunk_size=s[..., 0],
+                                           chunk_quality=s[..., 1], download_time=s[..., 2], rebuffer_time=s[..., 3])
+        check(lib().mansy_sim_lookahead(ctypes.byref(self.tables.c), ptr(self.state), self.n, ptr(plans), K, H,
+                                        ptr(b.qoe_parts) if per_step else None, ptr(b.scalars) if per_step else None, ptr(b.total),
+                                        ptr(b.steps), ptr(b.best), ptr(b.best_total), stream_ptr(self.device)), 'mansy_sim_lookahead')
+        return b.full if per_step else b.short
 
     def simulate_download(self, tile_rates, auto_reset=False, validate=False):
         """tile_rates: int32 cuda tensor [n,64], bitrate VERSION 0..4 per tile (values outside are clamped by the kernel; validate=True
@@ -191,6 +261,25 @@ class Simulator:
         assert over == (self.next_chunk > self.end_chunk)
         return (out.tile_size[0].cpu().numpy(), out.tile_quality[0].cpu().numpy(), int(sc[0]), float(sc[1]), download_time, rebuffer_time,
                 out.actual_viewport[0].cpu().numpy(), over)
+
+    def lookahead(self, plans):
+        """K candidate plans of H chunks each, downloaded virtually from where the session stands (BatchedSimulator.lookahead); the
+        session does not move.  plans: array-like [K,H,64] of versions 0..4.  Returns a namespace: total float32 [K], steps (int; the
+        chunks of the horizon the session still has, 0 when it is over), best (int; first candidate with the largest total),
+        qoe float32 [K,H,4] = qoe, qoe1, qoe2, qoe3 and scalars float64 [K,H,4] = chunk_size, chunk_quality, download_time, rebuffer_time
+        of every virtual step (rows t >= steps are zeros)."""
+        try:
+            p = np.asarray(plans)
+        except Exception as e:
+            raise MansyError(f'plans must be array-like [K, H, {N_TILE}]: {e}')
+        if p.ndim != 3 or p.shape[2] != N_TILE or p.dtype.kind not in 'iu' or not 1 <= p.shape[0] <= MAX_CANDIDATES or not 1 <= p.shape[1] <= MAX_HORIZON:
+            raise MansyError(f'plans must be integers [K, H, {N_TILE}] with 1 <= K <= {MAX_CANDIDATES} and 1 <= H <= {MAX_HORIZON}')
+        if (p < 0).any() or (p > N_RATE - 1).any():
+            raise MansyError(f'plans must hold versions in 0..{N_RATE - 1}')
+        dev_plans = torch.from_numpy(np.ascontiguousarray(p, dtype=np.int32)[None]).to(self.device)
+        out = self._sim.lookahead(dev_plans)
+        return types.SimpleNamespace(total=out.total[0].cpu().numpy(), steps=int(out.steps[0].item()), best=int(out.best[0].item()),
+                                     qoe=out.qoe_parts[0].cpu().numpy(), scalars=out.scalars[0].cpu().numpy())
 
     def reset(self):
         """Restarts the SAME session at chunk startup_download + 1 with an empty clock and the start-up buffer, as a freshly constructed

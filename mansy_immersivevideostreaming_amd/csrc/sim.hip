@@ -14,6 +14,10 @@
 // written.  ONE STATE BUFFER THEREFORE BELONGS EITHER TO A VECTOR ENVIRONMENT OR TO A SIMULATOR, NEVER TO BOTH.
 // A step reads 2 x 1280 B of manifest rows, 256 B of versions, 64 B of viewport map and a few trace bins; it writes 2 x 256 B of
 // tile rows, 64 B of viewport and ~50 B of scalars -- all of it as one coalesced 64-lane access per row.
+// What-if (mansy_sim_lookahead / mansy_sim_peek_ahead, ExpertEnv.choose_action's pattern, bitrate_selection/envs/expert_env.py:358-422):
+// K candidate plans of H chunks per session are downloaded virtually from the session's record, which is only read, with the same
+// arithmetic, so a virtual step returns the bits the committed step would; the forward peek shows the table rows of the chunks a caller
+// plans over.
 #include "mansy_kernels.h"
 #include "../../include/mansy_hip.h"
 
@@ -161,7 +165,172 @@ __global__ __launch_bounds__(256) void sim_peek_kernel(mansy_env_tables T, const
   if (pred) pred[row] = T.vp_pred[vrow + lane];
 }
 
-int check_sim_tables(const mansy_env_tables* T, const char* who) {     // the conditions env.hip's check_tables makes
+// ---- what-if: candidate plans downloaded virtually from a session's record, which is only read (expert_env.py:358-422 for arbitrary
+// tile versions).  LookState is the part of the record a download moves and a QoE term reads; it lives in registers of the wave
+// that walks one candidate and is dropped at the end.
+struct LookState { double cur_time, buf_size, bwc; int cur_idx, has_prev; float prev_vq, sum; };
+struct LookConst { const double* bw; int tlen; float w0, w1, w2, max_rate; double chunk_length; };
+
+// One virtual step by one wavefront (lane = tile): sim_download_kernel's arithmetic from "Simulator.simulate_download" to the QoE, line
+// for line, on the tile's size / quality of the planned version and the chunk's ground-truth viewport.  qoe_row / sc_row: this step's
+// four-value output rows (nullable, launch-uniform).
+__device__ __forceinline__ void look_step(LookState& s, const LookConst& c, int my_size, float tq, float gv, int lane, float* qoe_row,
+                                          double* sc_row) {
+  const int chunk_size = wave_isum(my_size);
+  const double start = s.cur_time;
+  double size = (double)chunk_size;
+  while (size > 0) {
+    const double fl = floor(s.cur_time + 1);
+    const double remain = (fl - s.cur_time) * s.bwc;
+    if (size >= remain) { s.cur_idx = s.cur_idx + 1 == c.tlen ? 0 : s.cur_idx + 1; s.bwc = c.bw[s.cur_idx]; s.cur_time = fl; size -= remain; }
+    else { s.cur_time += size / s.bwc; size = 0; }
+  }
+  const double download_time = s.cur_time - start;
+  double rebuf = 0.0;
+  if (download_time > s.buf_size) { rebuf = download_time - s.buf_size; s.buf_size = c.chunk_length; }
+  else s.buf_size = s.buf_size - download_time + c.chunk_length;
+  const ViewportSums vs = viewport_sums(gv, tq);
+  const float s_v = vs.s_v;
+  float vq = vs.s_vq / s_v;
+  const float s_var = var_sum(vs, gv, tq, vq);
+  const float intra = (s_var / s_v) / c.max_rate;
+  vq = vq / c.max_rate;
+  const float inter = s.has_prev ? fabsf(vq - s.prev_vq) : 0.f;
+  s.prev_vq = vq; s.has_prev = 1;
+  const float qoe1 = vq, qoe3 = intra + inter;
+  const float qoe = c.w0 * qoe1 - c.w1 * (float)rebuf - c.w2 * qoe3;
+  s.sum = s.sum + qoe;                       // ((0 + qoe_0) + qoe_1) + .. : plan_step's ps.sum (env.hip)
+  if (sc_row) {
+    const double chunk_quality = seq_dsum64(tq);
+    if (lane == 0) { sc_row[0] = (double)chunk_size; sc_row[1] = chunk_quality; sc_row[2] = download_time; sc_row[3] = rebuf; }
+  }
+  if (qoe_row && lane == 0) { qoe_row[0] = qoe; qoe_row[1] = qoe1; qoe_row[2] = (float)rebuf; qoe_row[3] = qoe3; }
+}
+
+struct LookTile { int size; float quality, gv; };
+// The table values lane's tile has in virtual step t: the planned version's size and quality (a 64-lane gather over the chunk's five
+// 256 B rows) and the ground-truth map.  mrow / vrow: this lane's element of the session's NEXT chunk.
+__device__ __forceinline__ LookTile look_load(const mansy_env_tables& T, const int* __restrict__ plan, size_t mrow, size_t vrow, int t) {
+  int ver = plan[(size_t)t * NTL];
+  ver = ver < 0 ? 0 : ver > NR - 1 ? NR - 1 : ver;
+  const size_t m = mrow + ((size_t)t * NR + ver) * NTL;
+  LookTile r;
+  r.size = T.size[m]; r.quality = T.quality[m]; r.gv = (float)T.vp_gt[vrow + (size_t)t * NTL];
+  return r;
+}
+
+// One wavefront per (session, candidate), lane = tile, looping over the horizon.  The loads of step t + 1 depend on t alone, not on
+// the download of step t, so they are issued before that step's dependent chain (trace walk, sequential sums) instead of behind it.
+// The K candidates of a session read the same table rows; they meet in the caches.  A form that staged the rows of the horizon in
+// LDS once per (session, 16 candidates) was measured and was not faster beyond the run-to-run spread, so
+// this plain form is the only one.
+__global__ __launch_bounds__(256) void sim_lookahead_kernel(mansy_env_tables T, const EnvState* __restrict__ st, int n, const int* __restrict__ plans,
+                                                            int K, int H, float* qoe_parts, double* scalars, float* total, int* steps_out) {
+  const long long wave = ((long long)blockIdx.x * 256 + threadIdx.x) >> 6;
+  const int lane = threadIdx.x & 63;
+  if (wave >= (long long)n * K) return;
+  const int e = __builtin_amdgcn_readfirstlane((int)(wave / K)), k = __builtin_amdgcn_readfirstlane((int)(wave % K));   // wave-uniform
+  const EnvState& r = st[e];
+  const int chunk = r.next_chunk, end_chunk = r.end_chunk;
+  int steps = session_closed(T, chunk, end_chunk) ? 0 : end_chunk - chunk + 1;
+  steps = steps < H ? steps : H;
+  const size_t cand = (size_t)e * K + k;
+  if (k == 0 && lane == 0) steps_out[e] = steps;
+  for (int t = steps; t < H; ++t) {          // steps that are not simulated: zeros, and no table row is touched for them
+    if (lane < 4) {
+      if (qoe_parts) qoe_parts[(cand * H + t) * 4 + lane] = 0.f;
+      if (scalars) scalars[(cand * H + t) * 4 + lane] = 0.0;
+    }
+  }
+  if (steps == 0) { if (lane == 0) total[cand] = 0.f; return; }
+  const int video = r.video, vp = r.vp;
+  const float* w = T.qoe_w + 3 * r.qoe;
+  LookConst c;
+  c.bw = T.trace_bw + (size_t)r.trace * T.trace_len_max; c.tlen = T.trace_len[r.trace];
+  c.w0 = w[0]; c.w1 = w[1]; c.w2 = w[2]; c.max_rate = (float)T.video_rates[NR - 1]; c.chunk_length = (double)T.chunk_length;
+  LookState s;
+  s.cur_time = r.cur_time; s.buf_size = r.buf_size; s.cur_idx = r.cur_idx; s.has_prev = r.has_prev; s.prev_vq = r.prev_vq; s.sum = 0.f;
+  s.bwc = c.bw[s.cur_idx];
+  const size_t mrow = ((size_t)video * T.n_chunk_max + chunk) * NR * NTL + lane;
+  const size_t vrow = ((size_t)vp * T.n_vpchunk_max + (chunk - T.vp_start[vp])) * NTL + lane;
+  const int* plan = plans + cand * H * NTL + lane;
+  LookTile next = look_load(T, plan, mrow, vrow, 0);
+  for (int t = 0; t < steps; ++t) {
+    const LookTile cur = next;
+    if (t + 1 < steps) next = look_load(T, plan, mrow, vrow, t + 1);
+    look_step(s, c, cur.size, cur.quality, cur.gv, lane, qoe_parts ? qoe_parts + (cand * H + t) * 4 : nullptr,
+              scalars ? scalars + (cand * H + t) * 4 : nullptr);
+  }
+  if (lane == 0) total[cand] = s.sum;
+}
+
+// (total, candidate) as one order-preserving 64-bit key: the larger total wins, then the smaller index; 0 for a NaN, which therefore
+// never beats anything.  The reference keeps the first plan with the strictly largest sum (`if best < qoe_sum`, expert_env.py:411).
+__device__ __forceinline__ unsigned long long total_key(float v, unsigned idx) {
+  if (v != v) return 0ull;
+  unsigned u = __float_as_uint(v == 0.f ? 0.f : v);                // -0.0 == 0.0 in that comparison
+  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return ((unsigned long long)u << 32) | (unsigned long long)(0xFFFFFFFFu - idx);
+}
+
+// One wavefront per session scans its K totals.  Every total a NaN (all keys 0): candidate 0.
+__global__ __launch_bounds__(256) void sim_best_kernel(const float* __restrict__ total, int n, int K, int* best, float* best_total) {
+  const int e = __builtin_amdgcn_readfirstlane((blockIdx.x * 256 + threadIdx.x) >> 6), lane = threadIdx.x & 63;   // wave-uniform
+  if (e >= n) return;
+  const float* row = total + (size_t)e * K;
+  unsigned long long key = 0ull;
+  for (int k = lane; k < K; k += NTL) {
+    const unsigned long long other = total_key(row[k], (unsigned)k);
+    key = other > key ? other : key;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long other = __shfl_xor(key, o, 64);
+    key = other > key ? other : key;
+  }
+  if (lane == 0) {
+    const int idx = key == 0ull ? 0 : (int)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull));
+    if (best) best[e] = idx;
+    if (best_total) best_total[e] = row[idx];
+  }
+}
+
+__global__ __launch_bounds__(256) void sim_peek_ahead_kernel(mansy_env_tables T, const EnvState* __restrict__ st, int n, int ahead, float* size,
+                                                             float* quality, unsigned char* gt, unsigned char* pred, double* acc,
+                                                             unsigned char* valid) {
+  const int e = __builtin_amdgcn_readfirstlane((blockIdx.x * 256 + threadIdx.x) >> 6), lane = threadIdx.x & 63;   // wave-uniform
+  if (e >= n) return;
+  const EnvState& s = st[e];
+  const int chunk = s.next_chunk + ahead, video = s.video, vp = s.vp;
+  const bool ok = !session_closed(T, s.next_chunk, s.end_chunk) && chunk <= s.end_chunk;
+  const size_t row = (size_t)e * NTL + lane;
+  if (lane == 0) valid[e] = ok ? 1 : 0;
+  if (!ok) {                                 // no table row belongs to a chunk past the session's end: zeros without a load
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+      if (size) size[((size_t)e * NR + r) * NTL + lane] = 0.f;
+      if (quality) quality[((size_t)e * NR + r) * NTL + lane] = 0.f;
+    }
+    if (gt) gt[row] = 0;
+    if (pred) pred[row] = 0;
+    if (acc && lane == 0) acc[e] = 0.0;
+    return;
+  }
+  const size_t mrow = ((size_t)video * T.n_chunk_max + chunk) * NR * NTL;
+#pragma unroll
+  for (int r = 0; r < NR; ++r) {
+    if (size) size[((size_t)e * NR + r) * NTL + lane] = (float)T.size[mrow + r * NTL + lane];
+    if (quality) quality[((size_t)e * NR + r) * NTL + lane] = T.quality[mrow + r * NTL + lane];
+  }
+  const size_t vcell = (size_t)vp * T.n_vpchunk_max + (chunk - T.vp_start[vp]);
+  if (gt) gt[row] = T.vp_gt[vcell * NTL + lane];
+  if (pred) pred[row] = T.vp_pred[vcell * NTL + lane];
+  // the accuracy a session shows when it reaches that chunk (do_reset / the step's acc_next read this table cell); the record's own copy
+  // for ahead == 0, as mansy_sim_peek shows it
+  if (acc && lane == 0) acc[e] = ahead == 0 ? s.last_chunk_accuracy : T.vp_acc[vcell];
+}
+
+int check_sim_tables(const mansy_env_tables* T, const char* who) {    // the conditions env.hip's check_tables makes
   MANSY_REQUIRE(T, "%s: null tables", who);
   MANSY_REQUIRE(T->size && T->quality && T->video_len && T->vp_gt && T->vp_pred && T->vp_acc && T->vp_start && T->vp_end && T->trace_bw &&
                     T->trace_len && T->samples && T->qoe_w, "%s: null table pointer", who);
@@ -193,6 +362,38 @@ int mansy_sim_peek(const mansy_env_tables* T, const void* state, int n, int* nex
   MANSY_REQUIRE(n >= 1, "sim_peek: n must be >= 1");
   MANSY_LAUNCH(sim_peek_kernel, dim3(mansy_ceil_div((long long)n * 64, 256)), dim3(256), 0, (hipStream_t)stream, *T, (const EnvState*)state, n,
                next_chunk, buffer, size, quality, gt, pred, acc);
+  MANSY_LAUNCH_CHECK();
+  return MANSY_OK;
+}
+
+int mansy_sim_lookahead(const mansy_env_tables* T, const void* state, int n, const int* plans, int K, int H, float* qoe_parts,
+                        double* scalars, float* total, int* steps, int* best, float* best_total, void* stream) {
+  int rc = check_sim_tables(T, "sim_lookahead"); if (rc) return rc;
+  MANSY_REQUIRE(state, "sim_lookahead: null state");
+  MANSY_REQUIRE(plans, "sim_lookahead: null plans");
+  MANSY_REQUIRE(total, "sim_lookahead: null total");
+  MANSY_REQUIRE(steps, "sim_lookahead: null steps");
+  MANSY_REQUIRE(n >= 1, "sim_lookahead: n must be >= 1");
+  MANSY_REQUIRE(K >= 1 && K <= MANSY_SIM_MAX_CANDIDATES, "sim_lookahead: K must be in [1, %d]", MANSY_SIM_MAX_CANDIDATES);
+  MANSY_REQUIRE(H >= 1 && H <= MANSY_SIM_MAX_HORIZON, "sim_lookahead: H must be in [1, %d]", MANSY_SIM_MAX_HORIZON);
+  MANSY_REQUIRE((long long)n * K < (1ll << 31), "sim_lookahead: n * K must be below 2^31");
+  MANSY_LAUNCH(sim_lookahead_kernel, dim3((unsigned)mansy_ceil_div((long long)n * K * 64, 256)), dim3(256), 0, (hipStream_t)stream, *T,
+               (const EnvState*)state, n, plans, K, H, qoe_parts, scalars, total, steps);
+  if (best || best_total)
+    MANSY_LAUNCH(sim_best_kernel, dim3(mansy_ceil_div((long long)n * 64, 256)), dim3(256), 0, (hipStream_t)stream, total, n, K, best, best_total);
+  MANSY_LAUNCH_CHECK();
+  return MANSY_OK;
+}
+
+int mansy_sim_peek_ahead(const mansy_env_tables* T, const void* state, int n, int ahead, float* size, float* quality, unsigned char* gt,
+                         unsigned char* pred, double* acc, unsigned char* valid, void* stream) {
+  int rc = check_sim_tables(T, "sim_peek_ahead"); if (rc) return rc;
+  MANSY_REQUIRE(state, "sim_peek_ahead: null state");
+  MANSY_REQUIRE(valid, "sim_peek_ahead: null valid");
+  MANSY_REQUIRE(n >= 1, "sim_peek_ahead: n must be >= 1");
+  MANSY_REQUIRE(ahead >= 0 && ahead < MANSY_SIM_MAX_HORIZON, "sim_peek_ahead: ahead must be in [0, %d)", MANSY_SIM_MAX_HORIZON);
+  MANSY_LAUNCH(sim_peek_ahead_kernel, dim3(mansy_ceil_div((long long)n * 64, 256)), dim3(256), 0, (hipStream_t)stream, *T, (const EnvState*)state, n,
+               ahead, size, quality, gt, pred, acc, valid);
   MANSY_LAUNCH_CHECK();
   return MANSY_OK;
 }
