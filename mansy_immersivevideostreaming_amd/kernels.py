@@ -136,6 +136,64 @@ def attn_bwd_packed(qkv, P, dout, H, drop=None):
     return dqkv
 
 
+def _addr(x):
+    """Device address of a tensor, or an address given as an int (a base offset into a slab: t.data_ptr() + 4 * floats)."""
+    return x.data_ptr() if isinstance(x, torch.Tensor) else int(x)
+
+
+def _dev(*xs):
+    return next((t.device for t in xs if isinstance(t, torch.Tensor)), torch.device('cuda', torch.cuda.current_device()))
+
+
+def _extent(nb, L, width, strides):
+    bs, rs = strides
+    return (nb - 1) * bs + (L - 1) * rs + width if nb > 0 else 0
+
+
+def attn_fwd(Q, K, V, nb, H, Lq, Lk, dh, q, k, v, o=None, scale=None, drop=None, out=None, P=None, save_p=True):
+    """General mansy_attn_fwd: Q / K / V / out / P are tensors or int device addresses; q / k / v / o are (batch stride, row stride)
+    pairs in floats.  scale None = 1/sqrt(dh).  out None: a fresh [nb, Lq, H*dh] (o defaults to its strides); P None: a fresh
+    [nb*H, Lq, Lk], or no probabilities at all with save_p=False.  Returns (out, P) as given / allocated."""
+    _gpu(*(t for t in (Q, K, V, out, P) if isinstance(t, torch.Tensor)))
+    d = H * dh
+    dev = _dev(Q, K, V, out, P)
+    if o is None:
+        o = (Lq * d, d)
+    if out is None:
+        assert tuple(o) in ((Lq * d, d), (d, 0)) and (Lq == 1 or o[1] == d), o
+        out = torch.empty(nb, Lq, d, dtype=torch.float32, device=dev)
+    if P is None and save_p:
+        P = torch.empty(nb * H, Lq, Lk, dtype=torch.float32, device=dev)
+    s = _attn_shape(nb, H, Lq, Lk, dh, q, k, v, o)
+    if scale is not None:
+        s.scale = scale
+    p, seed, site = drop if drop is not None else (0.0, 0, 0)
+    check(lib().mansy_attn_fwd(_addr(Q), _addr(K), _addr(V), _addr(out), _addr(P) if P is not None else None, ctypes.byref(s),
+                               p, seed, site, stream_ptr(dev)), 'mansy_attn_fwd')
+    return out, P
+
+
+def attn_bwd(Q, K, V, P, dO, nb, H, Lq, Lk, dh, q, k, v, o, scale=None, drop=None, accum_kv=False, dQ=None, dK=None, dV=None):
+    """General mansy_attn_bwd.  The gradients use the strides of their inputs (dQ: q, dK: k, dV: v; dO: o).  dQ / dK / dV None:
+    fresh zero-filled flat buffers of exactly the addressed extent.  accum_kv: dK / dV rows are added to.  Returns (dQ, dK, dV)."""
+    _gpu(*(t for t in (Q, K, V, P, dO, dQ, dK, dV) if isinstance(t, torch.Tensor)))
+    d = H * dh
+    dev = _dev(Q, K, V, P, dO)
+    if dQ is None:
+        dQ = torch.zeros(_extent(nb, Lq, d, q), dtype=torch.float32, device=dev)
+    if dK is None:
+        dK = torch.zeros(_extent(nb, Lk, d, k), dtype=torch.float32, device=dev)
+    if dV is None:
+        dV = torch.zeros(_extent(nb, Lk, d, v), dtype=torch.float32, device=dev)
+    s = _attn_shape(nb, H, Lq, Lk, dh, q, k, v, o)
+    if scale is not None:
+        s.scale = scale
+    p, seed, site = drop if drop is not None else (0.0, 0, 0)
+    check(lib().mansy_attn_bwd(_addr(Q), _addr(K), _addr(V), _addr(P), _addr(dO), _addr(dQ), _addr(dK), _addr(dV), ctypes.byref(s),
+                               p, seed, site, int(bool(accum_kv)), stream_ptr(dev)), 'mansy_attn_bwd')
+    return dQ, dK, dV
+
+
 def layernorm_fwd(a, b, w, bias, eps=1e-5):
     _gpu(a, w)
     rows, C = a.shape
@@ -182,8 +240,9 @@ def ln_partials_reduce(partials, dw, db):
     return dw, db
 
 
-def attn_cross_deferred(q_all, memkv, P_all, dO_all, H, drop_sites=None, p_drop=0.0, seed=0):
+def attn_cross_deferred(q_all, memkv, P_all, dO_all, H, drop_sites=None, p_drop=0.0, seed=0, accumulate=False, out=None):
     """Decoder cross-attention backward the engine's way: q_all / dO_all [T, B, d], memkv [B, M, 2d] (K | V), P_all [T, B*H, M].
+    out: the [B, M, 2d] gradient slab to write (None: a fresh one); accumulate: the gradients are added to out's contents.
     Returns (dq_all [T, B, d], dmemkv [B, M, 2d])."""
     _gpu(q_all, memkv, P_all, dO_all)
     T, B, d = q_all.shape
@@ -192,7 +251,11 @@ def attn_cross_deferred(q_all, memkv, P_all, dO_all, H, drop_sites=None, p_drop=
     dq = torch.empty_like(q_all)
     dS = torch.empty(T, B * H, M, dtype=torch.float32, device=q_all.device)
     Pk = torch.empty_like(dS)
-    dkv = torch.empty_like(memkv)
+    if out is not None:
+        _gpu(out)
+        assert out.shape == memkv.shape and out.dtype == torch.float32 and out.is_contiguous(), out.shape
+    assert out is not None or not accumulate, 'accumulate needs the slab to add to (out=)'
+    dkv = out if out is not None else torch.empty_like(memkv)
     kb = memkv.data_ptr()
     st = stream_ptr(q_all.device)
     for i in range(T):
@@ -200,8 +263,8 @@ def attn_cross_deferred(q_all, memkv, P_all, dO_all, H, drop_sites=None, p_drop=
         check(lib().mansy_attn_bwd_dq(ptr(q_all[i]), kb, kb + 4 * d, ptr(P_all[i]), ptr(dO_all[i]), ptr(dq[i]), ptr(dS[i]), ptr(Pk[i]),
                                       ctypes.byref(s), p_drop, seed, site, st), 'mansy_attn_bwd_dq')
     gb = dkv.data_ptr()
-    check(lib().mansy_attn_kvgrad(ptr(q_all), B * d, ptr(dO_all), B * d, ptr(dS), ptr(Pk), gb, gb + 4 * d, ctypes.byref(s), T, 0, st),
-          'mansy_attn_kvgrad')
+    check(lib().mansy_attn_kvgrad(ptr(q_all), B * d, ptr(dO_all), B * d, ptr(dS), ptr(Pk), gb, gb + 4 * d, ctypes.byref(s), T,
+                                  int(bool(accumulate)), st), 'mansy_attn_kvgrad')
     return dq, dkv
 
 
