@@ -231,6 +231,28 @@ int mansy_sim_lookahead(const mansy_env_tables* T, const void* state, int n, con
 int mansy_sim_peek_ahead(const mansy_env_tables* T, const void* state, int n, int ahead, float* size, float* quality, unsigned char* gt,
                          unsigned char* pred, double* acc, unsigned char* valid, void* stream);
 
+/* ------------------------------------------------------------------ batched simulator: candidate plans from byte budgets
+ * The step between mansy_sim_peek_ahead and mansy_sim_lookahead: per-tile VERSIONS for chunk next_chunk + t of session i, one allocation
+ * per (session i, candidate k, step t), made from a byte budget and a weight per tile by a greedy multiple-choice knapsack on that
+ * chunk's manifest rows.  `state` is only read.
+ * budgets f64 [n,K,H], in the units of the manifest sizes.  weights f32 [n,H,64] (shared by the K candidates), or NULL: the table's
+ * predicted map vp_pred of that chunk, converted to float.  plans i32 [n,K,H,64] (the layout mansy_sim_lookahead reads), plan_bytes i32
+ * [n,K,H] (nullable) = the chunk size of the plan, which is the chunk_size mansy_sim_lookahead reports for it, steps i32 [n] as
+ * mansy_sim_lookahead's.  Rows t >= steps[i]: zeros in plans and plan_bytes, written without touching a table.
+ * One allocation: every tile starts at version 0 and total = the integer sum of the 64 version-0 sizes.  A round looks at the NEXT
+ * version of every tile below version 4: dq = the float32 difference of the two qualities, gain = (double)weight * (double)dq, ds = the
+ * integer difference of the two sizes (it may be <= 0).  The tile is a candidate iff gain > 0 and (double)(total + ds) <= budget; its
+ * ratio is +inf for ds <= 0 and the float64 quotient gain / ds otherwise.  The candidate with the largest ratio is upgraded by one
+ * version and total += ds; AMONG EQUAL RATIOS THE LOWEST TILE INDEX WINS (all upgrades that cost no bytes are equal at +inf).  Candidates
+ * are looked at afresh every round (total may shrink, so a tile that did not fit may fit later); the allocation ends when a round has no
+ * candidate, after 256 rounds at the latest.
+ * A NaN weight, a NaN budget or a gain <= 0 never upgrades (the comparisons are false); a +inf budget applies every upgrade with a
+ * positive gain; a budget below the version-0 size (-inf included) leaves version 0 everywhere and plan_bytes = that size: the chunk is
+ * downloaded all the same, nothing is refused.  1 <= K <= MANSY_SIM_MAX_CANDIDATES, 1 <= H <= MANSY_SIM_MAX_HORIZON and n * K * H must
+ * stay below 2^31 (one wavefront per allocation). */
+int mansy_sim_allocate(const mansy_env_tables* T, const void* state, int n, const double* budgets, const float* weights, int K, int H,
+                       int* plans, int* plan_bytes, int* steps, void* stream);
+
 /* ------------------------------------------------------------------ MPC expert (demonstrations for behaviour cloning)
  * Replaces ExpertEnv._profile_viewport_qualities_sizes and ExpertEnv.choose_action (bitrate_selection/envs/
  * expert_env.py:126-181, 358-422) + ExpertSimulator.virtual_simulate_download_with_chunk_size /

@@ -9,7 +9,8 @@ bound that allocates on the ground-truth viewport.
 Both also answer "what would happen if" without moving a session: `lookahead(plans)` downloads K candidate plans of H chunks virtually
 from where every session stands (one launch, the state buffer is only read) and `peek(ahead=t)` shows the table rows of the chunks such
 plans are made for -- the pattern of the reference's own planner (ExpertEnv.choose_action, envs/expert_env.py:358-422) for arbitrary tile
-versions.
+versions.  `allocate(budgets, weights)` makes such plans: one greedy per-tile allocation under a byte budget per (session, candidate,
+chunk), on weights the caller brings or the predicted map, again without moving a session.
 
 The session records are the environment's (`mansy_env_init` / `mansy_env_reset`), so sessions walk the catalogue exactly as the
 environments of `MANSYVecEnv` do.  A state buffer belongs either to a `MANSYVecEnv` or to a simulator, never both: the simulator keeps no
@@ -62,6 +63,7 @@ class BatchedSimulator:
             over=self.over)
         self._peek_ahead = None               # peek(ahead > 0) has buffers of its own, made on first use
         self._look = {}                       # (K, H) -> lookahead()'s buffers and the two namespaces over them
+        self._alloc = {}                      # (K, H) -> allocate()'s buffers
 
     def reset(self):
         """Every session opens its next catalogue entry at chunk startup_download + 1 with an empty clock (MANSYEnv.reset's
@@ -145,6 +147,48 @@ class BatchedSimulator:
                                         ptr(b.qoe_parts) if per_step else None, ptr(b.scalars) if per_step else None, ptr(b.total),
                                         ptr(b.steps), ptr(b.best), ptr(b.best_total), stream_ptr(self.device)), 'mansy_sim_lookahead')
         return b.full if per_step else b.short
+
+    def allocate(self, budgets, weights=None):
+        """Candidate plans from byte budgets (mansy_sim_allocate): for every (session i, candidate k, step t) the tiles of chunk
+        next_chunk + t start at version 0 and the upgrade with the largest weight x quality gain per byte that still fits
+        budgets[i,k,t] is applied, round by round, until none fits (the lowest tile among equal ratios; an upgrade that costs no bytes
+        comes first; include/mansy_hip.h has the definition to the bit).  The sessions do not move: the state buffer is only read.
+        budgets: float64 cuda tensor [n,K,H], contiguous, in the units of the manifest sizes (peek()['size']); 1 <= K <= MAX_CANDIDATES,
+        1 <= H <= MAX_HORIZON.  weights: float32 cuda tensor [n,H,64], contiguous, the weight of every tile of chunk next_chunk + t
+        (shared by the K candidates), or None for the predicted map of that chunk (peek(ahead=t)['pred'] as floats).  A NaN budget, a NaN
+        weight or a weight <= 0 upgrades nothing; a budget below the size of version 0 leaves version 0 everywhere.
+        Returns a namespace of device tensors, without a synchronisation: plans i32 [n,K,H,64] (goes straight into `lookahead`),
+        plan_bytes i32 [n,K,H] (the chunk_size `lookahead` reports for the plan) and steps i32 [n] = min(H, chunks the session has left;
+        0 when it is over); rows t >= steps[i] are zeros.  The buffers are cached per (K, H) and overwritten by the next call with that
+        shape."""
+        if not isinstance(budgets, torch.Tensor) or budgets.dtype != torch.float64:
+            raise MansyError('budgets must be a float64 cuda tensor (there is no CPU path)')
+        if weights is not None and (not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32):
+            raise MansyError('weights must be a float32 cuda tensor or None (there is no CPU path)')
+        if budgets.dim() != 3 or budgets.shape[0] != self.n:
+            raise MansyError(f'budgets must have the shape [{self.n}, K, H], not {list(budgets.shape)}')
+        K, H = int(budgets.shape[1]), int(budgets.shape[2])
+        if weights is not None and tuple(weights.shape) != (self.n, H, N_TILE):
+            raise MansyError(f'weights must have the shape [{self.n}, H = {H}, {N_TILE}], not {list(weights.shape)}')
+        if not 1 <= K <= MAX_CANDIDATES:
+            raise MansyError(f'budgets holds K = {K} candidates per session: 1..{MAX_CANDIDATES} are supported')
+        if not 1 <= H <= MAX_HORIZON:
+            raise MansyError(f'budgets holds H = {H} steps per candidate: 1..{MAX_HORIZON} are supported')
+        if self.n * K * H >= 2 ** 31:
+            raise MansyError('n * K * H must stay below 2^31')
+        for name, x in (('budgets', budgets), ('weights', weights)):
+            if x is not None and (not x.is_cuda or x.device != self.state.device or not x.is_contiguous()):
+                raise MansyError(f'{name} must be a contiguous {str(x.dtype)[6:]} cuda tensor on {self.state.device} (there is no CPU path)')
+        b = self._alloc.get((K, H))
+        if b is None:
+            dev = self.device
+            b = types.SimpleNamespace(plans=torch.zeros(self.n, K, H, N_TILE, dtype=torch.int32, device=dev),
+                                      plan_bytes=torch.zeros(self.n, K, H, dtype=torch.int32, device=dev),
+                                      steps=torch.zeros(self.n, dtype=torch.int32, device=dev))
+            self._alloc[(K, H)] = b
+        check(lib().mansy_sim_allocate(ctypes.byref(self.tables.c), ptr(self.state), self.n, ptr(budgets), ptr(weights) if weights is not None else None,
+                                       K, H, ptr(b.plans), ptr(b.plan_bytes), ptr(b.steps), stream_ptr(self.device)), 'mansy_sim_allocate')
+        return b
 
     def simulate_download(self, tile_rates, auto_reset=False, validate=False):
         """tile_rates: int32 cuda tensor [n,64], bitrate VERSION 0..4 per tile (values outside are clamped by the kernel; validate=True
@@ -280,6 +324,24 @@ class Simulator:
         out = self._sim.lookahead(dev_plans)
         return types.SimpleNamespace(total=out.total[0].cpu().numpy(), steps=int(out.steps[0].item()), best=int(out.best[0].item()),
                                      qoe=out.qoe_parts[0].cpu().numpy(), scalars=out.scalars[0].cpu().numpy())
+
+    def allocate(self, budgets, weights=None):
+        """K candidate plans of H chunks made from byte budgets (BatchedSimulator.allocate); the session does not move.  budgets:
+        array-like [K,H] of numbers, weights: array-like [H,64] or None (the predicted maps).  Returns a namespace: plans int32
+        [K,H,64], plan_bytes int32 [K,H] and steps (int; rows t >= steps are zeros)."""
+        try:
+            b = np.asarray(budgets)
+            w = None if weights is None else np.asarray(weights)
+        except Exception as e:
+            raise MansyError(f'budgets must be array-like [K, H] and weights [H, {N_TILE}]: {e}')
+        if b.ndim != 2 or b.dtype.kind not in 'fiu' or not 1 <= b.shape[0] <= MAX_CANDIDATES or not 1 <= b.shape[1] <= MAX_HORIZON:
+            raise MansyError(f'budgets must be numbers [K, H] with 1 <= K <= {MAX_CANDIDATES} and 1 <= H <= {MAX_HORIZON}')
+        if w is not None and (w.dtype.kind not in 'fiu' or w.shape != (b.shape[1], N_TILE)):
+            raise MansyError(f'weights must be numbers [H = {b.shape[1]}, {N_TILE}] or None')
+        dev_b = torch.from_numpy(np.ascontiguousarray(b, dtype=np.float64)[None]).to(self.device)
+        dev_w = None if w is None else torch.from_numpy(np.ascontiguousarray(w, dtype=np.float32)[None]).to(self.device)
+        out = self._sim.allocate(dev_b, dev_w)
+        return types.SimpleNamespace(plans=out.plans[0].cpu().numpy(), plan_bytes=out.plan_bytes[0].cpu().numpy(), steps=int(out.steps[0].item()))
 
     def reset(self):
         """Restarts the SAME session at chunk startup_download + 1 with an empty clock and the start-up buffer, as a freshly constructed

@@ -18,6 +18,8 @@
 // K candidate plans of H chunks per session are downloaded virtually from the session's record, which is only read, with the same
 // arithmetic, so a virtual step returns the bits the committed step would; the forward peek shows the table rows of the chunks a caller
 // plans over.
+// Making the plans (mansy_sim_allocate): one greedy per-tile allocation under a byte budget per (session, candidate, step), on the same
+// table rows, from weights the caller brings or the predicted map.
 #include "mansy_kernels.h"
 #include "../../include/mansy_hip.h"
 
@@ -30,6 +32,19 @@ namespace {
 // A record no session is open in: past its last chunk, or never reset since mansy_env_init (next_chunk == 0 there).
 __device__ __forceinline__ bool session_closed(const mansy_env_tables& T, int next_chunk, int end_chunk) {
   return next_chunk > end_chunk || next_chunk <= T.startup_download;
+}
+// The chunks of a horizon of H the session still has: min(H, chunks left), 0 for a closed record.
+__device__ __forceinline__ int steps_ahead(const mansy_env_tables& T, int next_chunk, int end_chunk, int H) {
+  const int steps = session_closed(T, next_chunk, end_chunk) ? 0 : end_chunk - next_chunk + 1;
+  return steps < H ? steps : H;
+}
+// Row addressing: element of (version 0, tile 0) of a chunk's manifest rows (five rows of 64 follow one another; the next chunk's
+// begin NR * NTL further), and the cell of a chunk in the viewport tables (vp_acc: the cell, vp_gt / vp_pred: cell * NTL + tile).
+__device__ __forceinline__ size_t manifest_row(const mansy_env_tables& T, int video, int chunk) {
+  return ((size_t)video * T.n_chunk_max + chunk) * NR * NTL;
+}
+__device__ __forceinline__ size_t viewport_cell(const mansy_env_tables& T, int vp, int chunk) {
+  return (size_t)vp * T.n_vpchunk_max + (chunk - T.vp_start[vp]);
 }
 
 __device__ __forceinline__ double seq_dsum64(float x) {      // ((..(0 + x0) + x1) ..) + x63 in float64, tile order (Python sum of a list)
@@ -65,11 +80,11 @@ __global__ __launch_bounds__(256) void sim_download_kernel(mansy_env_tables T, E
   // ---- loads that depend on the state alone
   int ver = tile_rates[row];
   ver = ver < 0 ? 0 : ver > NR - 1 ? NR - 1 : ver;
-  const size_t mrow = ((size_t)s.video * T.n_chunk_max + chunk) * NR * NTL;
+  const size_t mrow = manifest_row(T, s.video, chunk);
   int size_r[NR]; float qual_r[NR];
 #pragma unroll
   for (int r = 0; r < NR; ++r) { size_r[r] = T.size[mrow + r * NTL + lane]; qual_r[r] = T.quality[mrow + r * NTL + lane]; }
-  const size_t vrow = ((size_t)s.vp * T.n_vpchunk_max + (chunk - T.vp_start[s.vp])) * NTL;
+  const size_t vrow = viewport_cell(T, s.vp, chunk) * NTL;
   const unsigned char gt = T.vp_gt[vrow + lane];
   const float gv = (float)gt;
   const float* w = T.qoe_w + 3 * s.qoe;
@@ -78,7 +93,7 @@ __global__ __launch_bounds__(256) void sim_download_kernel(mansy_env_tables T, E
   const int tlen = T.trace_len[s.trace];
   double bwc = bw[s.cur_idx];
   const bool over_pre = chunk + 1 > s.end_chunk;
-  const double acc_next = over_pre ? 0.0 : T.vp_acc[(size_t)s.vp * T.n_vpchunk_max + (chunk + 1 - T.vp_start[s.vp])];
+  const double acc_next = over_pre ? 0.0 : T.vp_acc[viewport_cell(T, s.vp, chunk + 1)];
   const float max_rate = (float)T.video_rates[NR - 1];
   // ---- Simulator.simulate_download
   int my_size = size_r[0]; float tq = qual_r[0];
@@ -154,13 +169,13 @@ __global__ __launch_bounds__(256) void sim_peek_kernel(mansy_env_tables T, const
     if (pred) pred[row] = 0;
     return;
   }
-  const size_t mrow = ((size_t)video * T.n_chunk_max + chunk) * NR * NTL;
+  const size_t mrow = manifest_row(T, video, chunk);
 #pragma unroll
   for (int r = 0; r < NR; ++r) {
     if (size) size[((size_t)e * NR + r) * NTL + lane] = (float)T.size[mrow + r * NTL + lane];
     if (quality) quality[((size_t)e * NR + r) * NTL + lane] = T.quality[mrow + r * NTL + lane];
   }
-  const size_t vrow = ((size_t)vp * T.n_vpchunk_max + (chunk - T.vp_start[vp])) * NTL;
+  const size_t vrow = viewport_cell(T, vp, chunk) * NTL;
   if (gt) gt[row] = T.vp_gt[vrow + lane];
   if (pred) pred[row] = T.vp_pred[vrow + lane];
 }
@@ -232,8 +247,7 @@ __global__ __launch_bounds__(256) void sim_lookahead_kernel(mansy_env_tables T, 
   const int e = __builtin_amdgcn_readfirstlane((int)(wave / K)), k = __builtin_amdgcn_readfirstlane((int)(wave % K));   // wave-uniform
   const EnvState& r = st[e];
   const int chunk = r.next_chunk, end_chunk = r.end_chunk;
-  int steps = session_closed(T, chunk, end_chunk) ? 0 : end_chunk - chunk + 1;
-  steps = steps < H ? steps : H;
+  const int steps = steps_ahead(T, chunk, end_chunk, H);
   const size_t cand = (size_t)e * K + k;
   if (k == 0 && lane == 0) steps_out[e] = steps;
   for (int t = steps; t < H; ++t) {          // steps that are not simulated: zeros, and no table row is touched for them
@@ -251,8 +265,8 @@ __global__ __launch_bounds__(256) void sim_lookahead_kernel(mansy_env_tables T, 
   LookState s;
   s.cur_time = r.cur_time; s.buf_size = r.buf_size; s.cur_idx = r.cur_idx; s.has_prev = r.has_prev; s.prev_vq = r.prev_vq; s.sum = 0.f;
   s.bwc = c.bw[s.cur_idx];
-  const size_t mrow = ((size_t)video * T.n_chunk_max + chunk) * NR * NTL + lane;
-  const size_t vrow = ((size_t)vp * T.n_vpchunk_max + (chunk - T.vp_start[vp])) * NTL + lane;
+  const size_t mrow = manifest_row(T, video, chunk) + lane;
+  const size_t vrow = viewport_cell(T, vp, chunk) * NTL + lane;
   const int* plan = plans + cand * H * NTL + lane;
   LookTile next = look_load(T, plan, mrow, vrow, 0);
   for (int t = 0; t < steps; ++t) {
@@ -316,13 +330,13 @@ __global__ __launch_bounds__(256) void sim_peek_ahead_kernel(mansy_env_tables T,
     if (acc && lane == 0) acc[e] = 0.0;
     return;
   }
-  const size_t mrow = ((size_t)video * T.n_chunk_max + chunk) * NR * NTL;
+  const size_t mrow = manifest_row(T, video, chunk);
 #pragma unroll
   for (int r = 0; r < NR; ++r) {
     if (size) size[((size_t)e * NR + r) * NTL + lane] = (float)T.size[mrow + r * NTL + lane];
     if (quality) quality[((size_t)e * NR + r) * NTL + lane] = T.quality[mrow + r * NTL + lane];
   }
-  const size_t vcell = (size_t)vp * T.n_vpchunk_max + (chunk - T.vp_start[vp]);
+  const size_t vcell = viewport_cell(T, vp, chunk);
   if (gt) gt[row] = T.vp_gt[vcell * NTL + lane];
   if (pred) pred[row] = T.vp_pred[vcell * NTL + lane];
   // the accuracy a session shows when it reaches that chunk (do_reset / the step's acc_next read this table cell); the record's own copy
@@ -330,7 +344,76 @@ __global__ __launch_bounds__(256) void sim_peek_ahead_kernel(mansy_env_tables T,
   if (acc && lane == 0) acc[e] = ahead == 0 ? s.last_chunk_accuracy : T.vp_acc[vcell];
 }
 
-int check_sim_tables(const mansy_env_tables* T, const char* who) {    // the conditions env.hip's check_tables makes
+// ---- budgeted per-tile allocation: the plans a look-ahead scores, made from a byte budget and a weight per tile.  One (session,
+// candidate, step) is a 64-item multiple-choice knapsack solved greedily: every tile starts at version 0 and, round by round, the
+// upgrade (one version up on one tile) with the largest gain per byte that still fits the budget is applied, gain = weight x quality
+// difference in float64, the lowest tile among equal ratios, an upgrade that costs no bytes before all that cost some (mansy_hip.h has
+// the definition to the bit).
+// The largest float64 of the wave, by xor shuffles: every lane ends up with it.  No NaN comes in here.
+__device__ __forceinline__ double wave_dmax(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { const double other = __shfl_xor(v, o, 64); v = other > v ? other : v; }
+  return v;
+}
+
+// One wavefront per (session, candidate, step), lane = tile.  The lane keeps its tile's five sizes and qualities in registers; the four
+// upgrades a tile can make do not depend on the round, so their byte differences, the signs of their gains and their ratios (the only
+// float64 divisions) are formed once and a round selects by the tile's version.  A round: 64-lane maximum of the candidates' ratios
+// (-1 stands for "not a candidate": a candidate's ratio is >= 0), ballot of the candidates that hold it, lowest set bit wins, and the
+// winner's byte difference reaches the wave-uniform total by readlane.  An empty ballot ends the loop, after 256 rounds at the latest.
+__global__ __launch_bounds__(256) void sim_allocate_kernel(mansy_env_tables T, const EnvState* __restrict__ st, int n, const double* __restrict__ budgets,
+                                                           const float* __restrict__ weights, int K, int H, int* plans, int* plan_bytes,
+                                                           int* steps_out) {
+  const long long wave = ((long long)blockIdx.x * 256 + threadIdx.x) >> 6;
+  const int lane = threadIdx.x & 63;
+  if (wave >= (long long)n * K * H) return;
+  const int KH = K * H;
+  const int e = __builtin_amdgcn_readfirstlane((int)(wave / KH)), kt = __builtin_amdgcn_readfirstlane((int)(wave % KH));   // wave-uniform
+  const int t = kt % H;
+  const EnvState& r = st[e];
+  const int chunk = r.next_chunk;
+  const int steps = steps_ahead(T, chunk, r.end_chunk, H);
+  if (kt == 0 && lane == 0) steps_out[e] = steps;
+  const size_t row = (size_t)wave;            // (e * K + k) * H + t
+  if (t >= steps) {                           // a chunk past the session's end: zeros, and no table row is touched for it
+    plans[row * NTL + lane] = 0;
+    if (plan_bytes && lane == 0) plan_bytes[row] = 0;
+    return;
+  }
+  const size_t mrow = manifest_row(T, r.video, chunk + t) + lane;
+  int size_r[NR]; float qual_r[NR];
+#pragma unroll
+  for (int v = 0; v < NR; ++v) { size_r[v] = T.size[mrow + v * NTL]; qual_r[v] = T.quality[mrow + v * NTL]; }
+  const float w = weights ? weights[((size_t)e * H + t) * NTL + lane] : (float)T.vp_pred[viewport_cell(T, r.vp, chunk + t) * NTL + lane];
+  const double budget = budgets[row];
+  int ds_u[NR - 1]; double ratio_u[NR - 1]; bool gain_u[NR - 1];
+#pragma unroll
+  for (int v = 0; v < NR - 1; ++v) {
+    const float dq = qual_r[v + 1] - qual_r[v];
+    const double gain = (double)w * (double)dq;
+    ds_u[v] = size_r[v + 1] - size_r[v];
+    gain_u[v] = gain > 0.0;                   // false for a NaN
+    ratio_u[v] = ds_u[v] <= 0 ? __builtin_huge_val() : gain / (double)ds_u[v];
+  }
+  int ver = 0, total = wave_isum(size_r[0]);
+  for (int round = 0; round < NTL * (NR - 1); ++round) {
+    int ds = 0; double ratio = -1.0; bool gains = false;         // ver == 4: no upgrade is left
+#pragma unroll
+    for (int v = 0; v < NR - 1; ++v) if (ver == v) { ds = ds_u[v]; ratio = ratio_u[v]; gains = gain_u[v]; }
+    const bool cand = gains && (double)(total + ds) <= budget;   // false for a NaN budget
+    const double key = cand ? ratio : -1.0;
+    const double top = wave_dmax(key);
+    const unsigned long long winners = __ballot(cand && key == top);
+    if (winners == 0ull) break;
+    const int win = __builtin_ctzll(winners);
+    total += __builtin_amdgcn_readlane(ds, win);
+    ver += lane == win ? 1 : 0;
+  }
+  plans[row * NTL + lane] = ver;
+  if (plan_bytes && lane == 0) plan_bytes[row] = total;
+}
+
+int check_sim_tables(const mansy_env_tables* T, const char* who) {   // the conditions env.hip's check_tables makes
   MANSY_REQUIRE(T, "%s: null tables", who);
   MANSY_REQUIRE(T->size && T->quality && T->video_len && T->vp_gt && T->vp_pred && T->vp_acc && T->vp_start && T->vp_end && T->trace_bw &&
                     T->trace_len && T->samples && T->qoe_w, "%s: null table pointer", who);
@@ -381,6 +464,23 @@ int mansy_sim_lookahead(const mansy_env_tables* T, const void* state, int n, con
                (const EnvState*)state, n, plans, K, H, qoe_parts, scalars, total, steps);
   if (best || best_total)
     MANSY_LAUNCH(sim_best_kernel, dim3(mansy_ceil_div((long long)n * 64, 256)), dim3(256), 0, (hipStream_t)stream, total, n, K, best, best_total);
+  MANSY_LAUNCH_CHECK();
+  return MANSY_OK;
+}
+
+int mansy_sim_allocate(const mansy_env_tables* T, const void* state, int n, const double* budgets, const float* weights, int K, int H,
+                       int* plans, int* plan_bytes, int* steps, void* stream) {
+  int rc = check_sim_tables(T, "sim_allocate"); if (rc) return rc;
+  MANSY_REQUIRE(state, "sim_allocate: null state");
+  MANSY_REQUIRE(budgets, "sim_allocate: null budgets");
+  MANSY_REQUIRE(plans, "sim_allocate: null plans");
+  MANSY_REQUIRE(steps, "sim_allocate: null steps");
+  MANSY_REQUIRE(n >= 1, "sim_allocate: n must be >= 1");
+  MANSY_REQUIRE(K >= 1 && K <= MANSY_SIM_MAX_CANDIDATES, "sim_allocate: K must be in [1, %d]", MANSY_SIM_MAX_CANDIDATES);
+  MANSY_REQUIRE(H >= 1 && H <= MANSY_SIM_MAX_HORIZON, "sim_allocate: H must be in [1, %d]", MANSY_SIM_MAX_HORIZON);
+  MANSY_REQUIRE((long long)n * K * H < (1ll << 31), "sim_allocate: n * K * H must be below 2^31");
+  MANSY_LAUNCH(sim_allocate_kernel, dim3((unsigned)mansy_ceil_div((long long)n * K * H * 64, 256)), dim3(256), 0, (hipStream_t)stream, *T,
+               (const EnvState*)state, n, budgets, weights, K, H, plans, plan_bytes, steps);
   MANSY_LAUNCH_CHECK();
   return MANSY_OK;
 }
