@@ -253,6 +253,29 @@ int mansy_sim_peek_ahead(const mansy_env_tables* T, const void* state, int n, in
 int mansy_sim_allocate(const mansy_env_tables* T, const void* state, int n, const double* budgets, const float* weights, int K, int H,
                        int* plans, int* plan_bytes, int* steps, void* stream);
 
+/* ------------------------------------------------------------------ batched simulator: sessions driven by the budget planner
+ * The receding-horizon loop of mansy_sim_allocate, mansy_sim_lookahead and mansy_sim_download for D decisions in ONE launch (one
+ * workgroup per session keeps the plans, the totals and the moving part of the record on chip).  fractions f64 [K]: budget fractions,
+ * one per candidate.  throughput f64 [n], IN AND OUT: the bytes/s estimate of every session.  Outputs per decision d: over u8 [n,D] and,
+ * all nullable, best i32 [n,D], best_total f32 [n,D], versions i32 [n,D,64] (the committed per-tile versions), qoe_parts f32 [n,D,4]
+ * and scalars f64 [n,D,4] of the committed step (mansy_sim_download's columns).
+ * For d = 0 .. D-1, for every session i independently:
+ *   1. budget[k] = (throughput[i] * (double)T.chunk_length) * fractions[k]: two float64 multiplies in that order; all H steps of
+ *      candidate k get the same budget.
+ *   2. plans[k][t] = what mansy_sim_allocate gives for that budget on chunk next_chunk + t with weights = NULL (the predicted map).
+ *   3. total[k], best and best_total = what mansy_sim_lookahead gives for those plans: the first candidate with the strictly largest
+ *      float32 total, a NaN never wins; a closed record has steps = 0, so its plans are zeros, its totals 0 and best 0.
+ *   4. plans[best][0] is committed exactly as mansy_sim_download would commit it, auto_reset included; versions, qoe_parts, scalars and
+ *      over of row d are that call's outputs.  A closed record without auto_reset: zeros, over = 1, the record stays untouched.
+ *   5. throughput[i] = download_time > 0 ? chunk_size / download_time : throughput[i], in float64, from that step's scalars.
+ * One call therefore returns the bits, and leaves the state buffer with the bytes, of D rounds of those three calls with steps 1 and 5
+ * done by the caller.  1 <= K <= MANSY_SIM_DRIVE_MAX_CANDIDATES (the K x H plans of one decision stay in 32 KB of LDS as bytes),
+ * 1 <= H <= MANSY_SIM_MAX_HORIZON, 1 <= D <= MANSY_SIM_DRIVE_MAX_DECISIONS, n >= 1. */
+#define MANSY_SIM_DRIVE_MAX_CANDIDATES 64
+#define MANSY_SIM_DRIVE_MAX_DECISIONS 256
+int mansy_sim_drive(const mansy_env_tables* T, void* state, int n, const double* fractions, int K, int H, int D, double* throughput, int* best,
+                    float* best_total, int* versions, float* qoe_parts, double* scalars, unsigned char* over, int auto_reset, void* stream);
+
 /* ------------------------------------------------------------------ MPC expert (demonstrations for behaviour cloning)
  * Replaces ExpertEnv._profile_viewport_qualities_sizes and ExpertEnv.choose_action (bitrate_selection/envs/
  * expert_env.py:126-181, 358-422) + ExpertSimulator.virtual_simulate_download_with_chunk_size /

@@ -10,7 +10,9 @@ Both also answer "what would happen if" without moving a session: `lookahead(pla
 from where every session stands (one launch, the state buffer is only read) and `peek(ahead=t)` shows the table rows of the chunks such
 plans are made for -- the pattern of the reference's own planner (ExpertEnv.choose_action, envs/expert_env.py:358-422) for arbitrary tile
 versions.  `allocate(budgets, weights)` makes such plans: one greedy per-tile allocation under a byte budget per (session, candidate,
-chunk), on weights the caller brings or the predicted map, again without moving a session.
+chunk), on weights the caller brings or the predicted map, again without moving a session.  `drive(fractions, horizon, decisions,
+throughput)` runs that planner closed-loop -- budgets from a throughput estimate, plans, scores, the best plan's first step committed,
+the estimate renewed -- for many decisions in one launch.
 
 The session records are the environment's (`mansy_env_init` / `mansy_env_reset`), so sessions walk the catalogue exactly as the
 environments of `MANSYVecEnv` do.  A state buffer belongs either to a `MANSYVecEnv` or to a simulator, never both: the simulator keeps no
@@ -26,6 +28,7 @@ from ..envs.mansy_env import OBS_LD, EnvTables
 
 N_TILE, N_RATE = 64, 5
 MAX_HORIZON, MAX_CANDIDATES = 8, 4096          # MANSY_SIM_MAX_HORIZON, MANSY_SIM_MAX_CANDIDATES of include/mansy_hip.h
+DRIVE_MAX_CANDIDATES, DRIVE_MAX_DECISIONS = 64, 256      # MANSY_SIM_DRIVE_MAX_CANDIDATES, MANSY_SIM_DRIVE_MAX_DECISIONS
 
 
 class BatchedSimulator:
@@ -64,6 +67,7 @@ class BatchedSimulator:
         self._peek_ahead = None               # peek(ahead > 0) has buffers of its own, made on first use
         self._look = {}                       # (K, H) -> lookahead()'s buffers and the two namespaces over them
         self._alloc = {}                      # (K, H) -> allocate()'s buffers
+        self._drive = {}                      # (K, H, D) -> drive()'s buffers and the two namespaces over them
 
     def reset(self):
         """Every session opens its next catalogue entry at chunk startup_download + 1 with an empty clock (MANSYEnv.reset's
@@ -189,6 +193,60 @@ class BatchedSimulator:
         check(lib().mansy_sim_allocate(ctypes.byref(self.tables.c), ptr(self.state), self.n, ptr(budgets), ptr(weights) if weights is not None else None,
                                        K, H, ptr(b.plans), ptr(b.plan_bytes), ptr(b.steps), stream_ptr(self.device)), 'mansy_sim_allocate')
         return b
+
+    def drive(self, fractions, horizon, decisions, throughput, auto_reset=False, per_tile=True):
+        """The planner loop `allocate` -> `lookahead` -> `simulate_download` -> throughput estimate for `decisions` decisions in ONE
+        launch (mansy_sim_drive): per decision and session, candidate k plans `horizon` chunks under the byte budget throughput x
+        chunk_length x fractions[k] on the predicted maps, the plans are scored, the first step of the best one is committed and
+        throughput becomes chunk_size / download_time of that step (unchanged where download_time is not > 0).  Every decision returns
+        the bits those calls would (include/mansy_hip.h has the definition), and the sessions move as D committed steps move them.
+        fractions: float64 cuda tensor [K], 1 <= K <= DRIVE_MAX_CANDIDATES; 1 <= horizon <= MAX_HORIZON; 1 <= decisions <=
+        DRIVE_MAX_DECISIONS; throughput: float64 cuda tensor [n], contiguous, bytes/s, UPDATED IN PLACE.  auto_reset as in
+        `simulate_download`; without it a session that ends inside the run gives zeros and over = 1 from then on.
+        Returns a namespace of device tensors, without a synchronisation: best i32 [n,D], best_total f32 [n,D], versions i32 [n,D,64]
+        (only with per_tile), qoe_parts f32 [n,D,4] with the views qoe, qoe1, qoe2, qoe3, scalars f64 [n,D,4] with the views chunk_size,
+        chunk_quality, download_time, rebuffer_time, over u8 [n,D] and throughput (the tensor handed in).  The buffers are cached per
+        (K, horizon, decisions) and overwritten by the next call with that shape."""
+        if not isinstance(fractions, torch.Tensor) or fractions.dtype != torch.float64:
+            raise MansyError('fractions must be a float64 cuda tensor (there is no CPU path)')
+        if not isinstance(throughput, torch.Tensor) or throughput.dtype != torch.float64:
+            raise MansyError('throughput must be a float64 cuda tensor (there is no CPU path)')
+        if fractions.dim() != 1:
+            raise MansyError(f'fractions must have the shape [K], not {list(fractions.shape)}')
+        if tuple(throughput.shape) != (self.n,):
+            raise MansyError(f'throughput must have the shape [{self.n}], not {list(throughput.shape)}')
+        K = int(fractions.shape[0])
+        if not 1 <= K <= DRIVE_MAX_CANDIDATES:
+            raise MansyError(f'fractions holds K = {K} candidates per session: 1..{DRIVE_MAX_CANDIDATES} are supported')
+        for name, x, hi in (('horizon', horizon, MAX_HORIZON), ('decisions', decisions, DRIVE_MAX_DECISIONS)):
+            if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or not 1 <= x <= hi:
+                raise MansyError(f'{name} must be an integer in 1..{hi}')
+        H, D = int(horizon), int(decisions)
+        for name, x in (('fractions', fractions), ('throughput', throughput)):
+            if not x.is_cuda or x.device != self.state.device or not x.is_contiguous():
+                raise MansyError(f'{name} must be a contiguous float64 cuda tensor on {self.state.device} (there is no CPU path)')
+        if auto_reset and getattr(self.tables, 'unvisitable', None):
+            raise MansyError('auto_reset walks the whole catalogue, but some of its entries hold no tables (negative slots in `samples`)')
+        b = self._drive.get((K, H, D))
+        if b is None:
+            dev = self.device
+            q = torch.zeros(self.n, D, 4, dtype=torch.float32, device=dev)
+            s = torch.zeros(self.n, D, 4, dtype=torch.float64, device=dev)
+            fields = dict(best=torch.zeros(self.n, D, dtype=torch.int32, device=dev), best_total=torch.zeros(self.n, D, dtype=torch.float32, device=dev),
+                          qoe_parts=q, qoe=q[..., 0], qoe1=q[..., 1], qoe2=q[..., 2], qoe3=q[..., 3], scalars=s, chunk_size=s[..., 0],
+                          chunk_quality=s[..., 1], download_time=s[..., 2], rebuffer_time=s[..., 3],
+                          over=torch.ones(self.n, D, dtype=torch.uint8, device=dev))
+            b = types.SimpleNamespace(versions=None, short=types.SimpleNamespace(**fields), full=None)
+            self._drive[(K, H, D)] = b
+        if per_tile and b.full is None:
+            b.versions = torch.zeros(self.n, D, N_TILE, dtype=torch.int32, device=self.device)
+            b.full = types.SimpleNamespace(versions=b.versions, **vars(b.short))
+        out = b.full if per_tile else b.short
+        out.throughput = throughput
+        check(lib().mansy_sim_drive(ctypes.byref(self.tables.c), ptr(self.state), self.n, ptr(fractions), K, H, D, ptr(throughput), ptr(out.best),
+                                    ptr(out.best_total), ptr(b.versions) if per_tile else None, ptr(out.qoe_parts), ptr(out.scalars),
+                                    ptr(out.over), int(bool(auto_reset)), stream_ptr(self.device)), 'mansy_sim_drive')
+        return out
 
     def simulate_download(self, tile_rates, auto_reset=False, validate=False):
         """tile_rates: int32 cuda tensor [n,64], bitrate VERSION 0..4 per tile (values outside are clamped by the kernel; validate=True
@@ -342,6 +400,39 @@ class Simulator:
         dev_w = None if w is None else torch.from_numpy(np.ascontiguousarray(w, dtype=np.float32)[None]).to(self.device)
         out = self._sim.allocate(dev_b, dev_w)
         return types.SimpleNamespace(plans=out.plans[0].cpu().numpy(), plan_bytes=out.plan_bytes[0].cpu().numpy(), steps=int(out.steps[0].item()))
+
+    def drive(self, fractions, horizon, decisions, throughput):
+        """`decisions` decisions of the budget planner on this session in one launch (BatchedSimulator.drive without auto_reset):
+        fractions array-like [K] of numbers, throughput a number (bytes/s).  Returns the new throughput estimate as a float.  The
+        decisions' outputs stay in `self.driven`, a namespace of numpy arrays: best [D], best_total [D], versions [D,64], qoe [D,4] =
+        qoe, qoe1, qoe2, qoe3, scalars [D,4] = chunk_size, chunk_quality, download_time, rebuffer_time, over [D] and steps (int; the
+        decisions that committed a chunk -- rows after the session's end are zeros with over = 1)."""
+        if self.next_chunk > self.end_chunk:
+            raise MansyError(f'the session is over (next chunk {self.next_chunk} > end chunk {self.end_chunk})')
+        try:
+            f = np.asarray(fractions)
+            thr = float(throughput)
+        except Exception as e:
+            raise MansyError(f'fractions must be array-like [K] and throughput a number: {e}')
+        if f.ndim != 1 or f.dtype.kind not in 'fiu' or not 1 <= f.shape[0] <= DRIVE_MAX_CANDIDATES:
+            raise MansyError(f'fractions must be numbers [K] with 1 <= K <= {DRIVE_MAX_CANDIDATES}')
+        dev_f = torch.from_numpy(np.ascontiguousarray(f, dtype=np.float64)).to(self.device)
+        dev_thr = torch.tensor([thr], dtype=torch.float64, device=self.device)
+        out = self._sim.drive(dev_f, horizon, decisions, dev_thr)
+        sc, over = out.scalars[0].cpu().numpy(), out.over[0].cpu().numpy()
+        chunk_length, steps = self.config.chunk_length, 0
+        for d in range(int(decisions)):        # the host mirrors, as simulate_download keeps them, up to the session's end
+            if self.next_chunk > self.end_chunk:
+                break
+            download_time = float(sc[d, 2])
+            self._buffer = chunk_length if download_time > self._buffer else self._buffer - download_time + chunk_length
+            self.next_chunk += 1
+            steps += 1
+            assert bool(over[d]) == (self.next_chunk > self.end_chunk)
+        self.driven = types.SimpleNamespace(best=out.best[0].cpu().numpy(), best_total=out.best_total[0].cpu().numpy(),
+                                            versions=out.versions[0].cpu().numpy(), qoe=out.qoe_parts[0].cpu().numpy(), scalars=sc, over=over,
+                                            steps=steps)
+        return float(dev_thr[0].item())
 
     def reset(self):
         """Restarts the SAME session at chunk startup_download + 1 with an empty clock and the start-up buffer, as a freshly constructed

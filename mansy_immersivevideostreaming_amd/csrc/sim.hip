@@ -20,6 +20,8 @@
 // plans over.
 // Making the plans (mansy_sim_allocate): one greedy per-tile allocation under a byte budget per (session, candidate, step), on the same
 // table rows, from weights the caller brings or the predicted map.
+// The planner loop (mansy_sim_drive): those three stages and the throughput estimate between them for D decisions per session in one
+// launch, one workgroup per session, built from the device helpers the stand-alone kernels run.
 #include "mansy_kernels.h"
 #include "../../include/mansy_hip.h"
 
@@ -54,31 +56,18 @@ __device__ __forceinline__ double seq_dsum64(float x) {      // ((..(0 + x0) + x
   return s;
 }
 
-__global__ __launch_bounds__(256) void sim_download_kernel(mansy_env_tables T, EnvState* st, int n, const int* __restrict__ tile_rates,
-                                                           float* tile_size, float* tile_quality, unsigned char* actual_viewport,
-                                                           double* scalars, float* qoe_parts, unsigned char* over_out, int auto_reset) {
-  const int e = __builtin_amdgcn_readfirstlane((blockIdx.x * 256 + threadIdx.x) >> 6), lane = threadIdx.x & 63;   // wave-uniform
-  if (e >= n) return;
-  const size_t row = (size_t)e * NTL + lane;
-  EnvRegs s;
-  load_state(s, st[e], lane);
-  if (session_closed(T, s.next_chunk, s.end_chunk)) {
-    if (!auto_reset) {                       // nothing to download: zeros, before any table is touched; the record stays as it is
-      if (tile_size) tile_size[row] = 0.f;
-      if (tile_quality) tile_quality[row] = 0.f;
-      if (actual_viewport) actual_viewport[row] = 0;
-      if (lane < 4) {
-        if (scalars) scalars[4 * e + lane] = 0.0;
-        if (qoe_parts) qoe_parts[4 * e + lane] = 0.f;
-      }
-      if (lane == 0) over_out[e] = 1;
-      return;
-    }
-    do_reset(T, s);
-  }
+// What a committed step hands back to the code around it (wave-uniform).
+struct Committed { int chunk_size; double download_time; bool over; };
+
+// One committed step by one wavefront (lane = tile) on the OPEN record s: Simulator.simulate_download, the QoE, the log and the step's
+// outputs, then the next catalogue entry if the session ended and auto_reset asks for it.  ver: this lane's version (clamped here).
+// The output pointers are the session's rows (tile rows of 64, scalars / qoe_parts rows of 4, one over flag; all but over nullable,
+// launch-uniform).  The record is not stored here.
+__device__ __forceinline__ Committed sim_commit(const mansy_env_tables& T, EnvRegs& s, int ver, int lane, float* tile_size, float* tile_quality,
+                                                unsigned char* actual_viewport, double* scalars, float* qoe_parts, unsigned char* over_out,
+                                                int auto_reset) {
   const int chunk = s.next_chunk;
   // ---- loads that depend on the state alone
-  int ver = tile_rates[row];
   ver = ver < 0 ? 0 : ver > NR - 1 ? NR - 1 : ver;
   const size_t mrow = manifest_row(T, s.video, chunk);
   int size_r[NR]; float qual_r[NR];
@@ -129,20 +118,49 @@ __global__ __launch_bounds__(256) void sim_download_kernel(mansy_env_tables T, E
   s.buffer0 = (float)s.buf_size;
   if (!over) s.last_chunk_accuracy = acc_next;
   // ---- outputs
-  if (tile_size) tile_size[row] = (float)my_size;
-  if (tile_quality) tile_quality[row] = tq;
-  if (actual_viewport) actual_viewport[row] = gt;
+  if (tile_size) tile_size[lane] = (float)my_size;
+  if (tile_quality) tile_quality[lane] = tq;
+  if (actual_viewport) actual_viewport[lane] = gt;
   if (scalars) {                             // (a launch-uniform branch: the 64-term double chain is skipped when nobody asks)
     const double chunk_quality = seq_dsum64(tq);
-    if (lane == 0) {
-      scalars[4 * e + 0] = (double)chunk_size; scalars[4 * e + 1] = chunk_quality; scalars[4 * e + 2] = download_time; scalars[4 * e + 3] = rebuf;
-    }
+    if (lane == 0) { scalars[0] = (double)chunk_size; scalars[1] = chunk_quality; scalars[2] = download_time; scalars[3] = rebuf; }
   }
   if (lane == 0) {
-    if (qoe_parts) { qoe_parts[4 * e + 0] = qoe; qoe_parts[4 * e + 1] = qoe1; qoe_parts[4 * e + 2] = (float)rebuf; qoe_parts[4 * e + 3] = qoe3; }
-    over_out[e] = over ? 1 : 0;
+    if (qoe_parts) { qoe_parts[0] = qoe; qoe_parts[1] = qoe1; qoe_parts[2] = (float)rebuf; qoe_parts[3] = qoe3; }
+    *over_out = over ? 1 : 0;
   }
   if (over && auto_reset) do_reset(T, s);    // the session opens its next catalogue entry, as the vector environment does
+  Committed c;
+  c.chunk_size = chunk_size; c.download_time = download_time; c.over = over;
+  return c;
+}
+
+__global__ __launch_bounds__(256) void sim_download_kernel(mansy_env_tables T, EnvState* st, int n, const int* __restrict__ tile_rates,
+                                                           float* tile_size, float* tile_quality, unsigned char* actual_viewport,
+                                                           double* scalars, float* qoe_parts, unsigned char* over_out, int auto_reset) {
+  const int e = __builtin_amdgcn_readfirstlane((blockIdx.x * 256 + threadIdx.x) >> 6), lane = threadIdx.x & 63;   // wave-uniform
+  if (e >= n) return;
+  const size_t row = (size_t)e * NTL + lane;
+  EnvRegs s;
+  load_state(s, st[e], lane);
+  if (session_closed(T, s.next_chunk, s.end_chunk)) {
+    if (!auto_reset) {                       // nothing to download: zeros, before any table is touched; the record stays as it is
+      if (tile_size) tile_size[row] = 0.f;
+      if (tile_quality) tile_quality[row] = 0.f;
+      if (actual_viewport) actual_viewport[row] = 0;
+      if (lane < 4) {
+        if (scalars) scalars[4 * e + lane] = 0.0;
+        if (qoe_parts) qoe_parts[4 * e + lane] = 0.f;
+      }
+      if (lane == 0) over_out[e] = 1;
+      return;
+    }
+    do_reset(T, s);
+  }
+  const size_t tiles = (size_t)e * NTL;
+  sim_commit(T, s, tile_rates[row], lane, tile_size ? tile_size + tiles : nullptr, tile_quality ? tile_quality + tiles : nullptr,
+             actual_viewport ? actual_viewport + tiles : nullptr, scalars ? scalars + 4 * (size_t)e : nullptr,
+             qoe_parts ? qoe_parts + 4 * (size_t)e : nullptr, over_out + e, auto_reset);
   store_state(st[e], s, lane);
 }
 
@@ -225,8 +243,7 @@ __device__ __forceinline__ void look_step(LookState& s, const LookConst& c, int 
 struct LookTile { int size; float quality, gv; };
 // The table values lane's tile has in virtual step t: the planned version's size and quality (a 64-lane gather over the chunk's five
 // 256 B rows) and the ground-truth map.  mrow / vrow: this lane's element of the session's NEXT chunk.
-__device__ __forceinline__ LookTile look_load(const mansy_env_tables& T, const int* __restrict__ plan, size_t mrow, size_t vrow, int t) {
-  int ver = plan[(size_t)t * NTL];
+__device__ __forceinline__ LookTile look_load(const mansy_env_tables& T, int ver, size_t mrow, size_t vrow, int t) {
   ver = ver < 0 ? 0 : ver > NR - 1 ? NR - 1 : ver;
   const size_t m = mrow + ((size_t)t * NR + ver) * NTL;
   LookTile r;
@@ -234,11 +251,49 @@ __device__ __forceinline__ LookTile look_load(const mansy_env_tables& T, const i
   return r;
 }
 
-// One wavefront per (session, candidate), lane = tile, looping over the horizon.  The loads of step t + 1 depend on t alone, not on
-// the download of step t, so they are issued before that step's dependent chain (trace walk, sequential sums) instead of behind it.
-// The K candidates of a session read the same table rows; they meet in the caches.  A form that staged the rows of the horizon in
-// LDS once per (session, 16 candidates) was measured and was not faster beyond the run-to-run spread, so
-// this plain form is the only one.
+// The fields of a record that planning reads: where the session stands and what a virtual download starts from.  The kernels that
+// only read a record take them from HBM; the driving kernel keeps them in LDS between the steps it commits.
+struct SessionView { int video, vp, trace, qoe, next_chunk, end_chunk, cur_idx, has_prev; double cur_time, buf_size; float prev_vq; };
+template <typename Rec>
+__device__ __forceinline__ SessionView view_of(const Rec& r) {
+  SessionView v;
+  v.video = r.video; v.vp = r.vp; v.trace = r.trace; v.qoe = r.qoe; v.next_chunk = r.next_chunk; v.end_chunk = r.end_chunk;
+  v.cur_idx = r.cur_idx; v.has_prev = r.has_prev; v.cur_time = r.cur_time; v.buf_size = r.buf_size; v.prev_vq = r.prev_vq;
+  return v;
+}
+
+// Where lane's versions of a plan come from: int32 rows of 64 in the caller's memory, or the byte rows the driving kernel keeps in LDS.
+struct PlanRows { const int* p; __device__ __forceinline__ int operator()(int t) const { return p[(size_t)t * NTL]; } };
+struct PlanBytes { const unsigned char* p; __device__ __forceinline__ int operator()(int t) const { return p[t * NTL]; } };
+
+// One candidate walked by one wavefront (lane = tile) over steps >= 1 chunks from where the session stands; returns the float32 total.
+// The loads of step t + 1 depend on t alone, not on the download of step t, so they are issued before that step's dependent chain
+// (trace walk, sequential sums) instead of behind it.  qoe_parts / scalars: the candidate's [H,4] rows (nullable, launch-uniform).
+template <typename Plan>
+__device__ __forceinline__ float look_walk(const mansy_env_tables& T, const SessionView& r, int steps, const Plan& plan, int lane, float* qoe_parts,
+                                           double* scalars) {
+  const int chunk = r.next_chunk;
+  const float* w = T.qoe_w + 3 * r.qoe;
+  LookConst c;
+  c.bw = T.trace_bw + (size_t)r.trace * T.trace_len_max; c.tlen = T.trace_len[r.trace];
+  c.w0 = w[0]; c.w1 = w[1]; c.w2 = w[2]; c.max_rate = (float)T.video_rates[NR - 1]; c.chunk_length = (double)T.chunk_length;
+  LookState s;
+  s.cur_time = r.cur_time; s.buf_size = r.buf_size; s.cur_idx = r.cur_idx; s.has_prev = r.has_prev; s.prev_vq = r.prev_vq; s.sum = 0.f;
+  s.bwc = c.bw[s.cur_idx];
+  const size_t mrow = manifest_row(T, r.video, chunk) + lane;
+  const size_t vrow = viewport_cell(T, r.vp, chunk) * NTL + lane;
+  LookTile next = look_load(T, plan(0), mrow, vrow, 0);
+  for (int t = 0; t < steps; ++t) {
+    const LookTile cur = next;
+    if (t + 1 < steps) next = look_load(T, plan(t + 1), mrow, vrow, t + 1);
+    look_step(s, c, cur.size, cur.quality, cur.gv, lane, qoe_parts ? qoe_parts + t * 4 : nullptr, scalars ? scalars + t * 4 : nullptr);
+  }
+  return s.sum;
+}
+
+// One wavefront per (session, candidate), lane = tile, looping over the horizon.  The K candidates of a session read the same table
+// rows; they meet in the caches.  A form that staged the rows of the horizon in LDS once per (session, 16 candidates) was measured and
+// was not faster beyond the run-to-run spread, so this plain form is the only one.
 __global__ __launch_bounds__(256) void sim_lookahead_kernel(mansy_env_tables T, const EnvState* __restrict__ st, int n, const int* __restrict__ plans,
                                                             int K, int H, float* qoe_parts, double* scalars, float* total, int* steps_out) {
   const long long wave = ((long long)blockIdx.x * 256 + threadIdx.x) >> 6;
@@ -246,8 +301,7 @@ __global__ __launch_bounds__(256) void sim_lookahead_kernel(mansy_env_tables T, 
   if (wave >= (long long)n * K) return;
   const int e = __builtin_amdgcn_readfirstlane((int)(wave / K)), k = __builtin_amdgcn_readfirstlane((int)(wave % K));   // wave-uniform
   const EnvState& r = st[e];
-  const int chunk = r.next_chunk, end_chunk = r.end_chunk;
-  const int steps = steps_ahead(T, chunk, end_chunk, H);
+  const int steps = steps_ahead(T, r.next_chunk, r.end_chunk, H);
   const size_t cand = (size_t)e * K + k;
   if (k == 0 && lane == 0) steps_out[e] = steps;
   for (int t = steps; t < H; ++t) {          // steps that are not simulated: zeros, and no table row is touched for them
@@ -257,25 +311,10 @@ __global__ __launch_bounds__(256) void sim_lookahead_kernel(mansy_env_tables T, 
     }
   }
   if (steps == 0) { if (lane == 0) total[cand] = 0.f; return; }
-  const int video = r.video, vp = r.vp;
-  const float* w = T.qoe_w + 3 * r.qoe;
-  LookConst c;
-  c.bw = T.trace_bw + (size_t)r.trace * T.trace_len_max; c.tlen = T.trace_len[r.trace];
-  c.w0 = w[0]; c.w1 = w[1]; c.w2 = w[2]; c.max_rate = (float)T.video_rates[NR - 1]; c.chunk_length = (double)T.chunk_length;
-  LookState s;
-  s.cur_time = r.cur_time; s.buf_size = r.buf_size; s.cur_idx = r.cur_idx; s.has_prev = r.has_prev; s.prev_vq = r.prev_vq; s.sum = 0.f;
-  s.bwc = c.bw[s.cur_idx];
-  const size_t mrow = manifest_row(T, video, chunk) + lane;
-  const size_t vrow = viewport_cell(T, vp, chunk) * NTL + lane;
-  const int* plan = plans + cand * H * NTL + lane;
-  LookTile next = look_load(T, plan, mrow, vrow, 0);
-  for (int t = 0; t < steps; ++t) {
-    const LookTile cur = next;
-    if (t + 1 < steps) next = look_load(T, plan, mrow, vrow, t + 1);
-    look_step(s, c, cur.size, cur.quality, cur.gv, lane, qoe_parts ? qoe_parts + (cand * H + t) * 4 : nullptr,
-              scalars ? scalars + (cand * H + t) * 4 : nullptr);
-  }
-  if (lane == 0) total[cand] = s.sum;
+  const PlanRows plan = {plans + cand * H * NTL + lane};
+  const float sum = look_walk(T, view_of(r), steps, plan, lane, qoe_parts ? qoe_parts + cand * H * 4 : nullptr,
+                              scalars ? scalars + cand * H * 4 : nullptr);
+  if (lane == 0) total[cand] = sum;
 }
 
 // (total, candidate) as one order-preserving 64-bit key: the larger total wins, then the smaller index; 0 for a NaN, which therefore
@@ -287,11 +326,8 @@ __device__ __forceinline__ unsigned long long total_key(float v, unsigned idx) {
   return ((unsigned long long)u << 32) | (unsigned long long)(0xFFFFFFFFu - idx);
 }
 
-// One wavefront per session scans its K totals.  Every total a NaN (all keys 0): candidate 0.
-__global__ __launch_bounds__(256) void sim_best_kernel(const float* __restrict__ total, int n, int K, int* best, float* best_total) {
-  const int e = __builtin_amdgcn_readfirstlane((blockIdx.x * 256 + threadIdx.x) >> 6), lane = threadIdx.x & 63;   // wave-uniform
-  if (e >= n) return;
-  const float* row = total + (size_t)e * K;
+// One wavefront scans the K totals of a session: the index of the best one, in every lane.  Every total a NaN (all keys 0): candidate 0.
+__device__ __forceinline__ int best_of(const float* row, int K, int lane) {
   unsigned long long key = 0ull;
   for (int k = lane; k < K; k += NTL) {
     const unsigned long long other = total_key(row[k], (unsigned)k);
@@ -302,8 +338,15 @@ __global__ __launch_bounds__(256) void sim_best_kernel(const float* __restrict__
     const unsigned long long other = __shfl_xor(key, o, 64);
     key = other > key ? other : key;
   }
+  return key == 0ull ? 0 : (int)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull));
+}
+
+__global__ __launch_bounds__(256) void sim_best_kernel(const float* __restrict__ total, int n, int K, int* best, float* best_total) {
+  const int e = __builtin_amdgcn_readfirstlane((blockIdx.x * 256 + threadIdx.x) >> 6), lane = threadIdx.x & 63;   // wave-uniform
+  if (e >= n) return;
+  const float* row = total + (size_t)e * K;
+  const int idx = best_of(row, K, lane);
   if (lane == 0) {
-    const int idx = key == 0ull ? 0 : (int)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull));
     if (best) best[e] = idx;
     if (best_total) best_total[e] = row[idx];
   }
@@ -349,18 +392,99 @@ __global__ __launch_bounds__(256) void sim_peek_ahead_kernel(mansy_env_tables T,
 // upgrade (one version up on one tile) with the largest gain per byte that still fits the budget is applied, gain = weight x quality
 // difference in float64, the lowest tile among equal ratios, an upgrade that costs no bytes before all that cost some (mansy_hip.h has
 // the definition to the bit).
-// The largest float64 of the wave, by xor shuffles: every lane ends up with it.  No NaN comes in here.
+// The largest float64 of the wave, in every lane.  No NaN comes in here, so the order of the comparisons does not show in the result:
+// DPP row rotations inside each row of 16 lanes, then the four rows by readlane (mansy_common.h's wave_max for two registers; a
+// __shfl_xor is an LDS-pipe round trip per register and step, and a round of the allocator waits for this maximum).
+template <int CTRL>
+__device__ __forceinline__ double dpp_f64(double v) {
+  const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
+  const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)u, CTRL, 0xf, 0xf, false);
+  const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(u >> 32), CTRL, 0xf, 0xf, false);
+  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+__device__ __forceinline__ double lane_f64(double v, int lane) {
+  const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
+  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)u, lane), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u >> 32), lane);
+  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+__device__ __forceinline__ double dmax2(double a, double b) { return b > a ? b : a; }
 __device__ __forceinline__ double wave_dmax(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { const double other = __shfl_xor(v, o, 64); v = other > v ? other : v; }
-  return v;
+  v = dmax2(v, dpp_f64<0x128>(v)); v = dmax2(v, dpp_f64<0x124>(v)); v = dmax2(v, dpp_f64<0x122>(v)); v = dmax2(v, dpp_f64<0x121>(v));
+  return dmax2(dmax2(lane_f64(v, 0), lane_f64(v, 16)), dmax2(lane_f64(v, 32), lane_f64(v, 48)));
 }
 
-// One wavefront per (session, candidate, step), lane = tile.  The lane keeps its tile's five sizes and qualities in registers; the four
-// upgrades a tile can make do not depend on the round, so their byte differences, the signs of their gains and their ratios (the only
-// float64 divisions) are formed once and a round selects by the tile's version.  A round: 64-lane maximum of the candidates' ratios
-// (-1 stands for "not a candidate": a candidate's ratio is >= 0), ballot of the candidates that hold it, lowest set bit wins, and the
-// winner's byte difference reaches the wave-uniform total by readlane.  An empty ballot ends the loop, after 256 rounds at the latest.
+// One allocation by one wavefront, lane = tile.  The lane keeps what its tile's four upgrades need in registers: they do not depend on
+// the round, so their byte differences, the signs of their gains and their ratios (the only float64 divisions) are formed once, from
+// the five sizes and qualities of the tile in chunk `chunk` of (video, vp) and the weights row w_row (64 floats) or, for w_row ==
+// nullptr, the chunk's predicted map.  base: the integer sum of the 64 version-0 sizes (wave-uniform).
+struct AllocTile { int ds_u[NR - 1]; double ratio_u[NR - 1]; bool gain_u[NR - 1]; int base; };
+__device__ __forceinline__ AllocTile alloc_tile(const mansy_env_tables& T, int video, int vp, int chunk, const float* __restrict__ w_row, int lane) {
+  const size_t mrow = manifest_row(T, video, chunk) + lane;
+  int size_r[NR]; float qual_r[NR];
+#pragma unroll
+  for (int v = 0; v < NR; ++v) { size_r[v] = T.size[mrow + v * NTL]; qual_r[v] = T.quality[mrow + v * NTL]; }
+  const float w = w_row ? w_row[lane] : (float)T.vp_pred[viewport_cell(T, vp, chunk) * NTL + lane];
+  AllocTile a;
+#pragma unroll
+  for (int v = 0; v < NR - 1; ++v) {
+    const float dq = qual_r[v + 1] - qual_r[v];
+    const double gain = (double)w * (double)dq;
+    a.ds_u[v] = size_r[v + 1] - size_r[v];
+    a.gain_u[v] = gain > 0.0;                 // false for a NaN
+    a.ratio_u[v] = a.ds_u[v] <= 0 ? __builtin_huge_val() : gain / (double)a.ds_u[v];
+  }
+  a.base = wave_isum(size_r[0]);
+  return a;
+}
+// The rounds of an allocation from round `round` on, where the lane's tile stands at version ver and the plan holds `total` bytes (0,
+// 0 and a.base: a whole allocation).  A round selects the tile's next upgrade by its version, then: 64-lane maximum of the candidates'
+// ratios (-1 stands for "not a candidate": a candidate's ratio is >= 0), ballot of the candidates that hold it, lowest set bit wins,
+// and the winner's byte difference reaches the wave-uniform total by readlane.  An empty ballot ends the loop, after 256 rounds at the
+// latest.  rec_win / rec_total (nullable): the winner and the total after every round that upgraded, for alloc_resume; returns the
+// number of those rounds, counted from 0.
+__device__ __forceinline__ int alloc_rounds(const AllocTile& a, double budget, int lane, int round, int& ver, int& total, unsigned char* rec_win,
+                                            int* rec_total) {
+  for (; round < NTL * (NR - 1); ++round) {
+    int ds = 0; double ratio = -1.0; bool gains = false;         // ver == 4: no upgrade is left
+#pragma unroll
+    for (int v = 0; v < NR - 1; ++v) if (ver == v) { ds = a.ds_u[v]; ratio = a.ratio_u[v]; gains = a.gain_u[v]; }
+    const bool cand = gains && (double)(total + ds) <= budget;   // false for a NaN budget
+    const double key = cand ? ratio : -1.0;
+    const double top = wave_dmax(key);
+    const unsigned long long winners = __ballot(cand && key == top);
+    if (winners == 0ull) break;
+    const int win = __builtin_ctzll(winners);
+    total += __builtin_amdgcn_readlane(ds, win);
+    ver += lane == win ? 1 : 0;
+    if (rec_win && lane == 0) { rec_win[round] = (unsigned char)win; rec_total[round] = total; }
+  }
+  return round;
+}
+// Where the allocation under `budget` stands after the rounds it shares with a recorded allocation of the same tiles under `lead`.
+// While the recorded winner of a round also fits `budget` it is this allocation's winner too: with budget <= lead this allocation's
+// candidates are a subset of the recorded one's (the fit test is the only place the budget enters), the recorded winner is the lowest
+// tile among the largest ratios of the superset, so where it belongs to the subset it is that of the subset as well, and the state
+// after the round is the same.  The first recorded round whose total does not fit ends the shared part (a NaN budget: round 0); the
+// rounds go on from there by alloc_rounds.  Not budget <= lead (a NaN on either side included): nothing is shared.  Returns the round
+// to go on from and sets the lane's version and the total there.
+__device__ __forceinline__ int alloc_resume(const AllocTile& a, double budget, double lead, int lane, const unsigned char* rec_win, const int* rec_total,
+                                            int rounds, int& ver, int& total) {
+  int shared = 0;
+  if (__ballot(budget <= lead) != 0ull) {
+    shared = rounds;
+    for (int r0 = 0; r0 < rounds; r0 += NTL) {
+      const int r = r0 + lane;
+      const unsigned long long fails = __ballot(r < rounds && !((double)rec_total[r < rounds ? r : 0] <= budget));
+      if (fails != 0ull) { shared = r0 + __builtin_ctzll(fails); break; }
+    }
+  }
+  ver = 0;
+  for (int r = 0; r < shared; ++r) ver += rec_win[r] == lane ? 1 : 0;
+  total = shared > 0 ? rec_total[shared - 1] : a.base;
+  return shared;
+}
+
+// One wavefront per (session, candidate, step).
 __global__ __launch_bounds__(256) void sim_allocate_kernel(mansy_env_tables T, const EnvState* __restrict__ st, int n, const double* __restrict__ budgets,
                                                            const float* __restrict__ weights, int K, int H, int* plans, int* plan_bytes,
                                                            int* steps_out) {
@@ -380,37 +504,131 @@ __global__ __launch_bounds__(256) void sim_allocate_kernel(mansy_env_tables T, c
     if (plan_bytes && lane == 0) plan_bytes[row] = 0;
     return;
   }
-  const size_t mrow = manifest_row(T, r.video, chunk + t) + lane;
-  int size_r[NR]; float qual_r[NR];
-#pragma unroll
-  for (int v = 0; v < NR; ++v) { size_r[v] = T.size[mrow + v * NTL]; qual_r[v] = T.quality[mrow + v * NTL]; }
-  const float w = weights ? weights[((size_t)e * H + t) * NTL + lane] : (float)T.vp_pred[viewport_cell(T, r.vp, chunk + t) * NTL + lane];
-  const double budget = budgets[row];
-  int ds_u[NR - 1]; double ratio_u[NR - 1]; bool gain_u[NR - 1];
-#pragma unroll
-  for (int v = 0; v < NR - 1; ++v) {
-    const float dq = qual_r[v + 1] - qual_r[v];
-    const double gain = (double)w * (double)dq;
-    ds_u[v] = size_r[v + 1] - size_r[v];
-    gain_u[v] = gain > 0.0;                   // false for a NaN
-    ratio_u[v] = ds_u[v] <= 0 ? __builtin_huge_val() : gain / (double)ds_u[v];
-  }
-  int ver = 0, total = wave_isum(size_r[0]);
-  for (int round = 0; round < NTL * (NR - 1); ++round) {
-    int ds = 0; double ratio = -1.0; bool gains = false;         // ver == 4: no upgrade is left
-#pragma unroll
-    for (int v = 0; v < NR - 1; ++v) if (ver == v) { ds = ds_u[v]; ratio = ratio_u[v]; gains = gain_u[v]; }
-    const bool cand = gains && (double)(total + ds) <= budget;   // false for a NaN budget
-    const double key = cand ? ratio : -1.0;
-    const double top = wave_dmax(key);
-    const unsigned long long winners = __ballot(cand && key == top);
-    if (winners == 0ull) break;
-    const int win = __builtin_ctzll(winners);
-    total += __builtin_amdgcn_readlane(ds, win);
-    ver += lane == win ? 1 : 0;
-  }
+  const AllocTile a = alloc_tile(T, r.video, r.vp, chunk + t, weights ? weights + ((size_t)e * H + t) * NTL : nullptr, lane);
+  int ver = 0, total = a.base;
+  alloc_rounds(a, budgets[row], lane, 0, ver, total, nullptr, nullptr);
   plans[row * NTL + lane] = ver;
   if (plan_bytes && lane == 0) plan_bytes[row] = total;
+}
+
+// ---- the planner loop in one launch: D decisions of allocate -> look-ahead -> commit -> throughput estimate per session, with the
+// plans, the totals and the record kept on chip (mansy_hip.h has the definition; every stage is the helper the stand-alone kernel of
+// that stage runs, so a decision returns the bits the three launches and the torch between them would).
+// One workgroup of WAVES wavefronts per session (16 or 4, chosen by the number of sessions), lane = tile.  LDS: K float32 totals, then
+// the K x H plans as bytes (version 0..4 of a tile), [k][t][tile] -- 32.25 KB at K = 64, H = 8 -- and the session's record with the
+// throughput estimate and the recorded rounds of the leading allocations (10 KB).  A decision:
+//   one wave per chunk makes the allocation under the largest budget and records its rounds      | barrier
+//   the waves share out the other allocations, each resumed where it leaves the recorded rounds  | barrier
+//   (rows t >= steps are never made: nothing reads them)
+//   the waves share out the K walks                                                              | barrier
+//   wave 0 picks the best and commits its first step on the record in LDS (registers in between) | barrier
+// EVERY WAVE REACHES EVERY BARRIER: D is a kernel argument, steps comes from the one record all waves read after the same barrier, and
+// no barrier stands inside a condition.  The record comes from HBM once and goes back once, after the last decision, if a step moved it.
+struct DriveShared {
+  EnvState rec; double throughput;
+  int rounds[MANSY_SIM_MAX_HORIZON], rec_total[MANSY_SIM_MAX_HORIZON][NTL * (NR - 1)];   // the leading allocation of every chunk, round by round
+  unsigned char rec_win[MANSY_SIM_MAX_HORIZON][NTL * (NR - 1)];
+};
+constexpr int DRIVE_WIDE_SESSIONS = 256;   // up to one session per CU of an MI355X: the wide workgroup
+
+template <int WAVES>
+__global__ __launch_bounds__(WAVES * 64) void sim_drive_kernel(mansy_env_tables T, EnvState* st, const double* __restrict__ fractions, int K, int H, int D,
+                                                               double* throughput, int* best, float* best_total, int* versions, float* qoe_parts,
+                                                               double* scalars, unsigned char* over_out, int auto_reset) {
+  extern __shared__ __align__(16) unsigned char drive_lds[];
+  __shared__ DriveShared sh;
+  float* totals = (float*)drive_lds;
+  unsigned char* plans = drive_lds + sizeof(float) * K;
+  const int e = blockIdx.x, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  bool moved = false;                         // wave 0's alone
+  if (wave == 0) {
+    EnvRegs s;
+    load_state(s, st[e], lane);
+    store_state(sh.rec, s, lane);
+    if (lane == 0) sh.throughput = throughput[e];
+  }
+  __syncthreads();
+  for (int d = 0; d < D; ++d) {
+    SessionView v = view_of(sh.rec);          // the same values in every lane of the workgroup; the integers into scalar registers
+    v.video = __builtin_amdgcn_readfirstlane(v.video); v.vp = __builtin_amdgcn_readfirstlane(v.vp);
+    v.trace = __builtin_amdgcn_readfirstlane(v.trace); v.qoe = __builtin_amdgcn_readfirstlane(v.qoe);
+    v.next_chunk = __builtin_amdgcn_readfirstlane(v.next_chunk); v.end_chunk = __builtin_amdgcn_readfirstlane(v.end_chunk);
+    v.cur_idx = __builtin_amdgcn_readfirstlane(v.cur_idx); v.has_prev = __builtin_amdgcn_readfirstlane(v.has_prev);
+    const int steps = steps_ahead(T, v.next_chunk, v.end_chunk, H);          // 0: a closed record, nothing to plan
+    const double thr = sh.throughput;
+    const double per_chunk = thr * (double)T.chunk_length;
+    // the candidate with the largest budget leads: one wave per chunk records its rounds, the others go on from the rounds they share
+    int lead_k = 0;
+    double lead = per_chunk * fractions[0];
+    for (int k = 1; k < K; ++k) {
+      const double budget = per_chunk * fractions[k];
+      if (__ballot(budget > lead) != 0ull) { lead = budget; lead_k = k; }
+    }
+    for (int t = wave; t < steps; t += WAVES) {
+      const AllocTile a = alloc_tile(T, v.video, v.vp, v.next_chunk + t, nullptr, lane);
+      int ver = 0, total = a.base;
+      const int rounds = alloc_rounds(a, lead, lane, 0, ver, total, sh.rec_win[t], sh.rec_total[t]);
+      if (lane == 0) sh.rounds[t] = rounds;
+      plans[(lead_k * H + t) * NTL + lane] = (unsigned char)ver;
+    }
+    __syncthreads();
+    const int KS = K * steps;
+    for (int kt = wave; kt < KS; kt += WAVES) {
+      const int k = kt / steps, t = kt - k * steps;
+      if (k == lead_k) continue;
+      const double budget = per_chunk * fractions[k];
+      const AllocTile a = alloc_tile(T, v.video, v.vp, v.next_chunk + t, nullptr, lane);
+      int ver, total;
+      const int round = alloc_resume(a, budget, lead, lane, sh.rec_win[t], sh.rec_total[t], __builtin_amdgcn_readfirstlane(sh.rounds[t]), ver, total);
+      alloc_rounds(a, budget, lane, round, ver, total, nullptr, nullptr);
+      plans[(k * H + t) * NTL + lane] = (unsigned char)ver;
+    }
+    __syncthreads();
+    if (steps > 0) {
+      for (int k = wave; k < K; k += WAVES) {
+        const PlanBytes plan = {plans + k * H * NTL + lane};
+        const float sum = look_walk(T, v, steps, plan, lane, nullptr, nullptr);
+        if (lane == 0) totals[k] = sum;
+      }
+    }
+    __syncthreads();
+    if (wave == 0) {
+      const size_t row = (size_t)e * D + d;
+      int b = 0, ver = 0;
+      float bt = 0.f;                         // a closed record: plans and totals are zeros, candidate 0
+      if (steps > 0) { b = best_of(totals, K, lane); bt = totals[b]; ver = plans[b * H * NTL + lane]; }
+      if (lane == 0) {
+        if (best) best[row] = b;
+        if (best_total) best_total[row] = bt;
+      }
+      if (versions) versions[row * NTL + lane] = ver;
+      if (steps == 0 && !auto_reset) {        // sim_download_kernel's closed path: zeros, and the record stays as it is
+        if (lane < 4) {
+          if (scalars) scalars[4 * row + lane] = 0.0;
+          if (qoe_parts) qoe_parts[4 * row + lane] = 0.f;
+        }
+        if (lane == 0) over_out[row] = 1;
+      } else {
+        EnvRegs s;
+        load_state(s, sh.rec, lane);
+        if (steps == 0) do_reset(T, s);
+        const Committed c = sim_commit(T, s, ver, lane, nullptr, nullptr, nullptr, scalars ? scalars + 4 * row : nullptr,
+                                       qoe_parts ? qoe_parts + 4 * row : nullptr, over_out + row, auto_reset);
+        store_state(sh.rec, s, lane);
+        if (lane == 0) sh.throughput = c.download_time > 0 ? (double)c.chunk_size / c.download_time : thr;
+        moved = true;
+      }
+    }
+    __syncthreads();
+  }
+  if (wave == 0) {
+    if (moved) {
+      EnvRegs s;
+      load_state(s, sh.rec, lane);
+      store_state(st[e], s, lane);
+    }
+    if (lane == 0) throughput[e] = sh.throughput;
+  }
 }
 
 int check_sim_tables(const mansy_env_tables* T, const char* who) {   // the conditions env.hip's check_tables makes
@@ -481,6 +699,30 @@ int mansy_sim_allocate(const mansy_env_tables* T, const void* state, int n, cons
   MANSY_REQUIRE((long long)n * K * H < (1ll << 31), "sim_allocate: n * K * H must be below 2^31");
   MANSY_LAUNCH(sim_allocate_kernel, dim3((unsigned)mansy_ceil_div((long long)n * K * H * 64, 256)), dim3(256), 0, (hipStream_t)stream, *T,
                (const EnvState*)state, n, budgets, weights, K, H, plans, plan_bytes, steps);
+  MANSY_LAUNCH_CHECK();
+  return MANSY_OK;
+}
+
+int mansy_sim_drive(const mansy_env_tables* T, void* state, int n, const double* fractions, int K, int H, int D, double* throughput, int* best,
+                    float* best_total, int* versions, float* qoe_parts, double* scalars, unsigned char* over, int auto_reset, void* stream) {
+  int rc = check_sim_tables(T, "sim_drive"); if (rc) return rc;
+  MANSY_REQUIRE(state, "sim_drive: null state");
+  MANSY_REQUIRE(fractions, "sim_drive: null fractions");
+  MANSY_REQUIRE(throughput, "sim_drive: null throughput");
+  MANSY_REQUIRE(over, "sim_drive: null over");
+  MANSY_REQUIRE(n >= 1, "sim_drive: n must be >= 1");
+  MANSY_REQUIRE(K >= 1 && K <= MANSY_SIM_DRIVE_MAX_CANDIDATES, "sim_drive: K must be in [1, %d]", MANSY_SIM_DRIVE_MAX_CANDIDATES);
+  MANSY_REQUIRE(H >= 1 && H <= MANSY_SIM_MAX_HORIZON, "sim_drive: H must be in [1, %d]", MANSY_SIM_MAX_HORIZON);
+  MANSY_REQUIRE(D >= 1 && D <= MANSY_SIM_DRIVE_MAX_DECISIONS, "sim_drive: D must be in [1, %d]", MANSY_SIM_DRIVE_MAX_DECISIONS);
+  const size_t lds = sizeof(float) * K + (size_t)K * H * NTL;      // the totals, then the plans as bytes
+  // few sessions: sixteen waves each, so that every CU works on the one session it holds; many: four, so that a CU holds several
+  // sessions whose serial parts (the leading allocations, the commit) overlap (DESIGN.md section 1 has the measurement)
+  if (n <= DRIVE_WIDE_SESSIONS)
+    MANSY_LAUNCH(sim_drive_kernel<16>, dim3((unsigned)n), dim3(16 * 64), lds, (hipStream_t)stream, *T, (EnvState*)state, fractions, K, H, D, throughput,
+                 best, best_total, versions, qoe_parts, scalars, over, auto_reset);
+  else
+    MANSY_LAUNCH(sim_drive_kernel<4>, dim3((unsigned)n), dim3(4 * 64), lds, (hipStream_t)stream, *T, (EnvState*)state, fractions, K, H, D, throughput,
+                 best, best_total, versions, qoe_parts, scalars, over, auto_reset);
   MANSY_LAUNCH_CHECK();
   return MANSY_OK;
 }
