@@ -275,6 +275,53 @@ int mansy_sim_allocate(const mansy_env_tables* T, const void* state, int n, cons
 #define MANSY_SIM_DRIVE_MAX_DECISIONS 256
 int mansy_sim_drive(const mansy_env_tables* T, void* state, int n, const double* fractions, int K, int H, int D, double* throughput, int* best,
                     float* best_total, int* versions, float* qoe_parts, double* scalars, unsigned char* over, int auto_reset, void* stream);
+/* The estimate is not cleared when auto_reset opens the next catalogue entry: mansy_sim_drive carries it across episodes. */
+
+/* ------------------------------------------------------------------ batched simulator: a client's look-ahead model for the planner
+ * mansy_sim_lookahead and mansy_sim_drive are an ORACLE: candidates are downloaded on the session's real trace, future bandwidth bins
+ * included, and scored on the ground-truth viewport of chunks the user has not watched yet.  A client that could be deployed plans with
+ * what it has: a throughput estimate made from the downloads it has finished, and the predicted viewport.  The two calls below score
+ * plans under that belief and keep the estimator; what is COMMITTED is always the truth (mansy_sim_download's step).
+ *
+ * Client look-ahead = mansy_sim_lookahead with two switches; everything else (steps, the closed-session rule, zero rows for t >= steps,
+ * total, best, best_total, clamping of versions, the limits on K and H) is unchanged.
+ *   viewport  MANSY_SIM_VIEW_GT (0): the QoE on vp_gt of chunk next_chunk + t, as mansy_sim_lookahead.  MANSY_SIM_VIEW_PRED (1): the same
+ *             QoE arithmetic with the vp_pred row of that chunk in its place; an all-zero map gives the NaN the reference gives (0 / 0).
+ *   throughput f64 [n], nullable.  NULL: the real trace walk, as mansy_sim_lookahead.  Otherwise download_time = (double)chunk_size /
+ *             throughput[i] for every step of every candidate of session i: plain IEEE double without special cases, so 0, a negative
+ *             value, inf and NaN give whatever the division and the two comparisons of the buffer rule (download_time > buffer) give.
+ *             The buffer rule, the QoE and the float32 running total are mansy_sim_lookahead's; the trace position of the record is
+ *             not read.
+ * With throughput = NULL and MANSY_SIM_VIEW_GT the call returns mansy_sim_lookahead's bits. */
+#define MANSY_SIM_VIEW_GT 0
+#define MANSY_SIM_VIEW_PRED 1
+int mansy_sim_lookahead_client(const mansy_env_tables* T, const void* state, int n, const int* plans, int K, int H, const double* throughput,
+                               int viewport, float* qoe_parts, double* scalars, float* total, int* steps, int* best, float* best_total,
+                               void* stream);
+/* Throughput estimator: the harmonic mean of the newest samples.  The caller owns two device buffers, read and written by the call:
+ * history f64 [n, MANSY_SIM_EST_MAX_WINDOW] (8 sample slots per session, THE NEWEST AT INDEX 7) and count i32 [n] (values read are
+ * clamped to 0..8).  After a committed step with download_time > 0:
+ *   sample = (double)chunk_size / download_time;
+ *   history[i][j] = history[i][j + 1] for j = 0..6, history[i][7] = sample;   count[i] = min(count[i] + 1, 8);
+ *   m = min(window, count[i]);
+ *   throughput[i] = m == 1 ? sample : (double)m / S,  S = (..(1.0 / history[i][8 - m] + 1.0 / history[i][9 - m]) + ..) + 1.0 / history[i][7],
+ * summed oldest first in double, without contraction.  Otherwise (no step committed, or download_time not > 0) throughput, history and
+ * count stay as they are.  1 <= window <= 8.  auto_reset does NOT clear the history: like mansy_sim_drive's estimate it is carried
+ * across episodes; a caller that wants a fresh client per episode zeroes history and count.
+ *
+ * Client drive = mansy_sim_drive's composition with these stages swapped in:
+ *   3. total, best and best_total come from the client look-ahead with `viewport` as given and throughput = the session's current
+ *      estimate when network == MANSY_SIM_NET_ESTIMATE (1), NULL (the trace) when network == MANSY_SIM_NET_TRACE (0).
+ *   4. plans[best][0] is committed on the truth, exactly as mansy_sim_download commits it (unchanged).
+ *   5. the estimate is renewed by the estimator above instead of the last-sample rule.
+ * With MANSY_SIM_NET_TRACE, MANSY_SIM_VIEW_GT and window = 1 the call returns mansy_sim_drive's bits, and history then holds the
+ * samples.  history and count are required; the other arguments and limits are mansy_sim_drive's. */
+#define MANSY_SIM_NET_TRACE 0
+#define MANSY_SIM_NET_ESTIMATE 1
+#define MANSY_SIM_EST_MAX_WINDOW 8
+int mansy_sim_drive_client(const mansy_env_tables* T, void* state, int n, const double* fractions, int K, int H, int D, double* throughput,
+                           int network, int viewport, int window, double* history, int* count, int* best, float* best_total, int* versions,
+                           float* qoe_parts, double* scalars, unsigned char* over, int auto_reset, void* stream);
 
 /* ------------------------------------------------------------------ MPC expert (demonstrations for behaviour cloning)
  * Replaces ExpertEnv._profile_viewport_qualities_sizes and ExpertEnv.choose_action (bitrate_selection/envs/

@@ -12,7 +12,9 @@ plans are made for -- the pattern of the reference's own planner (ExpertEnv.choo
 versions.  `allocate(budgets, weights)` makes such plans: one greedy per-tile allocation under a byte budget per (session, candidate,
 chunk), on weights the caller brings or the predicted map, again without moving a session.  `drive(fractions, horizon, decisions,
 throughput)` runs that planner closed-loop -- budgets from a throughput estimate, plans, scores, the best plan's first step committed,
-the estimate renewed -- for many decisions in one launch.
+the estimate renewed -- for many decisions in one launch.  `lookahead` and `drive` are an oracle (the real trace and the ground-truth
+viewport of chunks not yet watched); `lookahead_client` and `drive_client` score the plans as a client that could be deployed has to --
+at a throughput estimate made from finished downloads and on the predicted viewport -- and commit on the truth.
 
 The session records are the environment's (`mansy_env_init` / `mansy_env_reset`), so sessions walk the catalogue exactly as the
 environments of `MANSYVecEnv` do.  A state buffer belongs either to a `MANSYVecEnv` or to a simulator, never both: the simulator keeps no
@@ -29,6 +31,15 @@ from ..envs.mansy_env import OBS_LD, EnvTables
 N_TILE, N_RATE = 64, 5
 MAX_HORIZON, MAX_CANDIDATES = 8, 4096          # MANSY_SIM_MAX_HORIZON, MANSY_SIM_MAX_CANDIDATES of include/mansy_hip.h
 DRIVE_MAX_CANDIDATES, DRIVE_MAX_DECISIONS = 64, 256      # MANSY_SIM_DRIVE_MAX_CANDIDATES, MANSY_SIM_DRIVE_MAX_DECISIONS
+EST_MAX_WINDOW = 8                                        # MANSY_SIM_EST_MAX_WINDOW: the sample slots of the throughput estimator
+VIEWPORTS = {'gt': 0, 'pred': 1}                          # MANSY_SIM_VIEW_GT, MANSY_SIM_VIEW_PRED
+NETWORKS = {'trace': 0, 'estimate': 1}                    # MANSY_SIM_NET_TRACE, MANSY_SIM_NET_ESTIMATE
+
+
+def _choice(name, value, table):
+    if not isinstance(value, str) or value not in table:
+        raise MansyError(f'{name} must be one of {sorted(table)}, not {value!r}')
+    return table[value]
 
 
 class BatchedSimulator:
@@ -68,6 +79,11 @@ class BatchedSimulator:
         self._look = {}                       # (K, H) -> lookahead()'s buffers and the two namespaces over them
         self._alloc = {}                      # (K, H) -> allocate()'s buffers
         self._drive = {}                      # (K, H, D) -> drive()'s buffers and the two namespaces over them
+        self._look_client = {}                # (K, H) -> lookahead_client()'s buffers, its own
+        self._drive_client = {}               # (K, H, D) -> drive_client()'s buffers, its own
+        # the throughput estimator of drive_client(): eight sample slots per session (the newest last) and how many are filled
+        self.history = torch.zeros(self.n, EST_MAX_WINDOW, **f64)
+        self.count = torch.zeros(self.n, dtype=torch.int32, device=dev)
 
     def reset(self):
         """Every session opens its next catalogue entry at chunk startup_download + 1 with an empty clock (MANSYEnv.reset's
@@ -80,6 +96,13 @@ class BatchedSimulator:
         self._worker = (self._worker + self.worker_num) % n_sample
         obs = torch.empty(self.n, OBS_LD, dtype=torch.float32, device=self.device)     # mansy_env_reset writes an observation: dropped
         check(lib().mansy_env_reset(ctypes.byref(self.tables.c), ptr(self.state), self.n, ptr(obs), stream_ptr(self.device)), 'mansy_env_reset')
+        return self
+
+    def reset_estimator(self):
+        """Empties the throughput estimator of `drive_client` (`history` and `count` become zeros).  `reset()` and auto_reset leave the
+        samples alone: an estimate is carried across episodes, as plain `drive` carries its own."""
+        self.history.zero_()
+        self.count.zero_()
         return self
 
     def peek(self, ahead=0):
@@ -108,6 +131,25 @@ class BatchedSimulator:
                                    ptr(p['quality']), ptr(p['gt']), ptr(p['pred']), ptr(p['acc']), stream_ptr(self.device)), 'mansy_sim_peek')
         return p
 
+    def _look_buffers(self, cache, K, H, per_step):
+        """The output buffers of a look-ahead of K candidates x H steps and the two namespaces over them, made on first use."""
+        b = cache.get((K, H))
+        if b is None:
+            dev = self.device
+            b = types.SimpleNamespace(total=torch.zeros(self.n, K, dtype=torch.float32, device=dev), steps=torch.zeros(self.n, dtype=torch.int32, device=dev),
+                                      best=torch.zeros(self.n, dtype=torch.int32, device=dev), best_total=torch.zeros(self.n, dtype=torch.float32, device=dev),
+                                      qoe_parts=None, scalars=None, short=None, full=None)
+            b.short = types.SimpleNamespace(total=b.total, steps=b.steps, best=b.best, best_total=b.best_total)
+            cache[(K, H)] = b
+        if per_step and b.full is None:
+            b.qoe_parts = torch.zeros(self.n, K, H, 4, dtype=torch.float32, device=self.device)
+            b.scalars = torch.zeros(self.n, K, H, 4, dtype=torch.float64, device=self.device)
+            q, s = b.qoe_parts, b.scalars
+            b.full = types.SimpleNamespace(total=b.total, steps=b.steps, best=b.best, best_total=b.best_total, qoe_parts=q, qoe=q[..., 0],
+                                           qoe1=q[..., 1], qoe2=q[..., 2], qoe3=q[..., 3], scalars=s, chunk_size=s[..., 0],
+                                           chunk_quality=s[..., 1], download_time=s[..., 2], rebuffer_time=s[..., 3])
+        return b
+
     def lookahead(self, plans, per_step=True):
         """What would happen if: K candidate plans per session downloaded VIRTUALLY over H chunks from where the session stands, with
         the real trace and the ground-truth viewport (the pattern of ExpertEnv.choose_action, expert_env.py:358-422, for arbitrary tile
@@ -132,21 +174,7 @@ class BatchedSimulator:
             raise MansyError('n * K must stay below 2^31')
         if not plans.is_cuda or plans.device != self.state.device or not plans.is_contiguous():
             raise MansyError(f'plans must be a contiguous int32 cuda tensor on {self.state.device} (there is no CPU path)')
-        b = self._look.get((K, H))
-        if b is None:
-            dev = self.device
-            b = types.SimpleNamespace(total=torch.zeros(self.n, K, dtype=torch.float32, device=dev), steps=torch.zeros(self.n, dtype=torch.int32, device=dev),
-                                      best=torch.zeros(self.n, dtype=torch.int32, device=dev), best_total=torch.zeros(self.n, dtype=torch.float32, device=dev),
-                                      qoe_parts=None, scalars=None, short=None, full=None)
-            b.short = types.SimpleNamespace(total=b.total, steps=b.steps, best=b.best, best_total=b.best_total)
-            self._look[(K, H)] = b
-        if per_step and b.full is None:
-            b.qoe_parts = torch.zeros(self.n, K, H, 4, dtype=torch.float32, device=self.device)
-            b.scalars = torch.zeros(self.n, K, H, 4, dtype=torch.float64, device=self.device)
-            q, s = b.qoe_parts, b.scalars
-            b.full = types.SimpleNamespace(total=b.total, steps=b.steps, best=b.best, best_total=b.best_total, qoe_parts=q, qoe=q[..., 0],
-                                           qoe1=q[..., 1], qoe2=q[..., 2], qoe3=q[..., 3], scalars=s, chunk_size=s[..., 0],
-                                           chunk_quality=s[..., 1], download_time=s[..., 2], rebuffer_time=s[..., 3])
+        b = self._look_buffers(self._look, K, H, per_step)
         check(lib().mansy_sim_lookahead(ctypes.byref(self.tables.c), ptr(self.state), self.n, ptr(plans), K, H,
                                         ptr(b.qoe_parts) if per_step else None, ptr(b.scalars) if per_step else None, ptr(b.total),
                                         ptr(b.steps), ptr(b.best), ptr(b.best_total), stream_ptr(self.device)), 'mansy_sim_lookahead')
@@ -194,6 +222,26 @@ class BatchedSimulator:
                                        K, H, ptr(b.plans), ptr(b.plan_bytes), ptr(b.steps), stream_ptr(self.device)), 'mansy_sim_allocate')
         return b
 
+    def _drive_buffers(self, cache, K, H, D, per_tile, throughput, **more):
+        """The output buffers of a driven run of D decisions and the namespace the call returns (`more`: further fields of it)."""
+        b = cache.get((K, H, D))
+        if b is None:
+            dev = self.device
+            q = torch.zeros(self.n, D, 4, dtype=torch.float32, device=dev)
+            s = torch.zeros(self.n, D, 4, dtype=torch.float64, device=dev)
+            fields = dict(best=torch.zeros(self.n, D, dtype=torch.int32, device=dev), best_total=torch.zeros(self.n, D, dtype=torch.float32, device=dev),
+                          qoe_parts=q, qoe=q[..., 0], qoe1=q[..., 1], qoe2=q[..., 2], qoe3=q[..., 3], scalars=s, chunk_size=s[..., 0],
+                          chunk_quality=s[..., 1], download_time=s[..., 2], rebuffer_time=s[..., 3],
+                          over=torch.ones(self.n, D, dtype=torch.uint8, device=dev), **more)
+            b = types.SimpleNamespace(versions=None, short=types.SimpleNamespace(**fields), full=None)
+            cache[(K, H, D)] = b
+        if per_tile and b.full is None:
+            b.versions = torch.zeros(self.n, D, N_TILE, dtype=torch.int32, device=self.device)
+            b.full = types.SimpleNamespace(versions=b.versions, **vars(b.short))
+        out = b.full if per_tile else b.short
+        out.throughput = throughput
+        return b, out
+
     def drive(self, fractions, horizon, decisions, throughput, auto_reset=False, per_tile=True):
         """The planner loop `allocate` -> `lookahead` -> `simulate_download` -> throughput estimate for `decisions` decisions in ONE
         launch (mansy_sim_drive): per decision and session, candidate k plans `horizon` chunks under the byte budget throughput x
@@ -227,25 +275,82 @@ class BatchedSimulator:
                 raise MansyError(f'{name} must be a contiguous float64 cuda tensor on {self.state.device} (there is no CPU path)')
         if auto_reset and getattr(self.tables, 'unvisitable', None):
             raise MansyError('auto_reset walks the whole catalogue, but some of its entries hold no tables (negative slots in `samples`)')
-        b = self._drive.get((K, H, D))
-        if b is None:
-            dev = self.device
-            q = torch.zeros(self.n, D, 4, dtype=torch.float32, device=dev)
-            s = torch.zeros(self.n, D, 4, dtype=torch.float64, device=dev)
-            fields = dict(best=torch.zeros(self.n, D, dtype=torch.int32, device=dev), best_total=torch.zeros(self.n, D, dtype=torch.float32, device=dev),
-                          qoe_parts=q, qoe=q[..., 0], qoe1=q[..., 1], qoe2=q[..., 2], qoe3=q[..., 3], scalars=s, chunk_size=s[..., 0],
-                          chunk_quality=s[..., 1], download_time=s[..., 2], rebuffer_time=s[..., 3],
-                          over=torch.ones(self.n, D, dtype=torch.uint8, device=dev))
-            b = types.SimpleNamespace(versions=None, short=types.SimpleNamespace(**fields), full=None)
-            self._drive[(K, H, D)] = b
-        if per_tile and b.full is None:
-            b.versions = torch.zeros(self.n, D, N_TILE, dtype=torch.int32, device=self.device)
-            b.full = types.SimpleNamespace(versions=b.versions, **vars(b.short))
-        out = b.full if per_tile else b.short
-        out.throughput = throughput
+        b, out = self._drive_buffers(self._drive, K, H, D, per_tile, throughput)
         check(lib().mansy_sim_drive(ctypes.byref(self.tables.c), ptr(self.state), self.n, ptr(fractions), K, H, D, ptr(throughput), ptr(out.best),
                                     ptr(out.best_total), ptr(b.versions) if per_tile else None, ptr(out.qoe_parts), ptr(out.scalars),
                                     ptr(out.over), int(bool(auto_reset)), stream_ptr(self.device)), 'mansy_sim_drive')
+        return out
+
+    def lookahead_client(self, plans, throughput, viewport='pred', per_step=True):
+        """`lookahead` under a client's belief (mansy_sim_lookahead_client): the virtual downloads take chunk_size / throughput[i]
+        seconds instead of walking the session's real trace, and the steps are scored on the predicted viewport instead of the ground
+        truth.  throughput: float64 cuda tensor [n] (bytes/s; the values are not validated: 0, negative, inf and NaN give what IEEE
+        double gives), or None for the real trace.  viewport: 'pred' or 'gt'.  With None and 'gt' the result equals `lookahead`'s.
+        plans, per_step and the returned namespaces are `lookahead`'s; the buffers are this method's own, cached per (K, H)."""
+        if not isinstance(plans, torch.Tensor) or plans.dtype != torch.int32:
+            raise MansyError('plans must be an int32 cuda tensor (there is no CPU path)')
+        if throughput is not None and (not isinstance(throughput, torch.Tensor) or throughput.dtype != torch.float64):
+            raise MansyError('throughput must be a float64 cuda tensor or None (there is no CPU path)')
+        if plans.dim() != 4 or plans.shape[0] != self.n or plans.shape[3] != N_TILE:
+            raise MansyError(f'plans must have the shape [{self.n}, K, H, {N_TILE}], not {list(plans.shape)}')
+        if throughput is not None and tuple(throughput.shape) != (self.n,):
+            raise MansyError(f'throughput must have the shape [{self.n}], not {list(throughput.shape)}')
+        K, H = int(plans.shape[1]), int(plans.shape[2])
+        if not 1 <= K <= MAX_CANDIDATES:
+            raise MansyError(f'plans holds K = {K} candidates per session: 1..{MAX_CANDIDATES} are supported')
+        if not 1 <= H <= MAX_HORIZON:
+            raise MansyError(f'plans holds H = {H} steps per candidate: 1..{MAX_HORIZON} are supported')
+        if self.n * K >= 2 ** 31:
+            raise MansyError('n * K must stay below 2^31')
+        view = _choice('viewport', viewport, VIEWPORTS)
+        for name, x in (('plans', plans), ('throughput', throughput)):
+            if x is not None and (not x.is_cuda or x.device != self.state.device or not x.is_contiguous()):
+                raise MansyError(f'{name} must be a contiguous {str(x.dtype)[6:]} cuda tensor on {self.state.device} (there is no CPU path)')
+        b = self._look_buffers(self._look_client, K, H, per_step)
+        check(lib().mansy_sim_lookahead_client(ctypes.byref(self.tables.c), ptr(self.state), self.n, ptr(plans), K, H,
+                                               ptr(throughput) if throughput is not None else None, view,
+                                               ptr(b.qoe_parts) if per_step else None, ptr(b.scalars) if per_step else None, ptr(b.total),
+                                               ptr(b.steps), ptr(b.best), ptr(b.best_total), stream_ptr(self.device)), 'mansy_sim_lookahead_client')
+        return b.full if per_step else b.short
+
+    def drive_client(self, fractions, horizon, decisions, throughput, window=5, viewport='pred', network='estimate', auto_reset=False,
+                     per_tile=True):
+        """`drive` as a client that could be deployed would run it (mansy_sim_drive_client): the candidates are scored by
+        `lookahead_client` -- on the predicted viewport ('pred') and, with network='estimate', at the session's current throughput
+        estimate instead of the real trace ('trace') -- while the best plan's first step is committed on the truth, as
+        `simulate_download` commits it.  After every committed step with download_time > 0 the estimate becomes the harmonic mean of
+        the newest min(window, samples so far) values of chunk_size / download_time, 1 <= window <= EST_MAX_WINDOW.  The samples live
+        in `self.history` f64 [n,8] (the newest at index 7) and `self.count` i32 [n], which this simulator owns: zeros at construction
+        and after `reset_estimator()`; `reset()` and auto_reset leave them alone, so an estimate is carried across episodes (as plain
+        `drive` carries its own).  With window=1, viewport='gt', network='trace' the call returns `drive`'s bits.
+        The other arguments are `drive`'s.  Returns `drive`'s namespace plus history and count, in buffers of its own, cached per
+        (K, horizon, decisions), without a synchronisation."""
+        if not isinstance(fractions, torch.Tensor) or fractions.dtype != torch.float64:
+            raise MansyError('fractions must be a float64 cuda tensor (there is no CPU path)')
+        if not isinstance(throughput, torch.Tensor) or throughput.dtype != torch.float64:
+            raise MansyError('throughput must be a float64 cuda tensor (there is no CPU path)')
+        if fractions.dim() != 1:
+            raise MansyError(f'fractions must have the shape [K], not {list(fractions.shape)}')
+        if tuple(throughput.shape) != (self.n,):
+            raise MansyError(f'throughput must have the shape [{self.n}], not {list(throughput.shape)}')
+        K = int(fractions.shape[0])
+        if not 1 <= K <= DRIVE_MAX_CANDIDATES:
+            raise MansyError(f'fractions holds K = {K} candidates per session: 1..{DRIVE_MAX_CANDIDATES} are supported')
+        for name, x, hi in (('horizon', horizon, MAX_HORIZON), ('decisions', decisions, DRIVE_MAX_DECISIONS), ('window', window, EST_MAX_WINDOW)):
+            if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or not 1 <= x <= hi:
+                raise MansyError(f'{name} must be an integer in 1..{hi}')
+        H, D = int(horizon), int(decisions)
+        view, net = _choice('viewport', viewport, VIEWPORTS), _choice('network', network, NETWORKS)
+        for name, x in (('fractions', fractions), ('throughput', throughput)):
+            if not x.is_cuda or x.device != self.state.device or not x.is_contiguous():
+                raise MansyError(f'{name} must be a contiguous float64 cuda tensor on {self.state.device} (there is no CPU path)')
+        if auto_reset and getattr(self.tables, 'unvisitable', None):
+            raise MansyError('auto_reset walks the whole catalogue, but some of its entries hold no tables (negative slots in `samples`)')
+        b, out = self._drive_buffers(self._drive_client, K, H, D, per_tile, throughput, history=self.history, count=self.count)
+        check(lib().mansy_sim_drive_client(ctypes.byref(self.tables.c), ptr(self.state), self.n, ptr(fractions), K, H, D, ptr(throughput), net, view,
+                                           int(window), ptr(self.history), ptr(self.count), ptr(out.best), ptr(out.best_total),
+                                           ptr(b.versions) if per_tile else None, ptr(out.qoe_parts), ptr(out.scalars), ptr(out.over),
+                                           int(bool(auto_reset)), stream_ptr(self.device)), 'mansy_sim_drive_client')
         return out
 
     def simulate_download(self, tile_rates, auto_reset=False, validate=False):
@@ -419,9 +524,53 @@ class Simulator:
         dev_f = torch.from_numpy(np.ascontiguousarray(f, dtype=np.float64)).to(self.device)
         dev_thr = torch.tensor([thr], dtype=torch.float64, device=self.device)
         out = self._sim.drive(dev_f, horizon, decisions, dev_thr)
+        self._mirror_driven(out, int(decisions))
+        return float(dev_thr[0].item())
+
+    def lookahead_client(self, plans, throughput, viewport='pred'):
+        """`lookahead` under a client's belief (BatchedSimulator.lookahead_client): throughput a number (bytes/s) or None for the real
+        trace, viewport 'pred' or 'gt'.  Returns `lookahead`'s namespace."""
+        try:
+            p = np.asarray(plans)
+            thr = None if throughput is None else float(throughput)
+        except Exception as e:
+            raise MansyError(f'plans must be array-like [K, H, {N_TILE}] and throughput a number or None: {e}')
+        if p.ndim != 3 or p.shape[2] != N_TILE or p.dtype.kind not in 'iu' or not 1 <= p.shape[0] <= MAX_CANDIDATES or not 1 <= p.shape[1] <= MAX_HORIZON:
+            raise MansyError(f'plans must be integers [K, H, {N_TILE}] with 1 <= K <= {MAX_CANDIDATES} and 1 <= H <= {MAX_HORIZON}')
+        if (p < 0).any() or (p > N_RATE - 1).any():
+            raise MansyError(f'plans must hold versions in 0..{N_RATE - 1}')
+        _choice('viewport', viewport, VIEWPORTS)
+        dev_plans = torch.from_numpy(np.ascontiguousarray(p, dtype=np.int32)[None]).to(self.device)
+        dev_thr = None if thr is None else torch.tensor([thr], dtype=torch.float64, device=self.device)
+        out = self._sim.lookahead_client(dev_plans, dev_thr, viewport)
+        return types.SimpleNamespace(total=out.total[0].cpu().numpy(), steps=int(out.steps[0].item()), best=int(out.best[0].item()),
+                                     qoe=out.qoe_parts[0].cpu().numpy(), scalars=out.scalars[0].cpu().numpy())
+
+    def drive_client(self, fractions, horizon, decisions, throughput, window=5, viewport='pred', network='estimate'):
+        """`drive` as a deployable client runs it (BatchedSimulator.drive_client without auto_reset).  Returns the new estimate as a
+        float; the decisions' outputs stay in `self.driven` as `drive` leaves them, plus history float64 [8] (the newest sample last)
+        and count (int).  `reset()` empties the estimator."""
+        if self.next_chunk > self.end_chunk:
+            raise MansyError(f'the session is over (next chunk {self.next_chunk} > end chunk {self.end_chunk})')
+        try:
+            f = np.asarray(fractions)
+            thr = float(throughput)
+        except Exception as e:
+            raise MansyError(f'fractions must be array-like [K] and throughput a number: {e}')
+        if f.ndim != 1 or f.dtype.kind not in 'fiu' or not 1 <= f.shape[0] <= DRIVE_MAX_CANDIDATES:
+            raise MansyError(f'fractions must be numbers [K] with 1 <= K <= {DRIVE_MAX_CANDIDATES}')
+        dev_f = torch.from_numpy(np.ascontiguousarray(f, dtype=np.float64)).to(self.device)
+        dev_thr = torch.tensor([thr], dtype=torch.float64, device=self.device)
+        out = self._sim.drive_client(dev_f, horizon, decisions, dev_thr, window=window, viewport=viewport, network=network)
+        self._mirror_driven(out, int(decisions))
+        self.driven.history, self.driven.count = out.history[0].cpu().numpy(), int(out.count[0].item())
+        return float(dev_thr[0].item())
+
+    def _mirror_driven(self, out, decisions):
+        """The host mirrors after a driven run, as simulate_download keeps them, up to the session's end; fills `self.driven`."""
         sc, over = out.scalars[0].cpu().numpy(), out.over[0].cpu().numpy()
         chunk_length, steps = self.config.chunk_length, 0
-        for d in range(int(decisions)):        # the host mirrors, as simulate_download keeps them, up to the session's end
+        for d in range(decisions):
             if self.next_chunk > self.end_chunk:
                 break
             download_time = float(sc[d, 2])
@@ -432,12 +581,12 @@ class Simulator:
         self.driven = types.SimpleNamespace(best=out.best[0].cpu().numpy(), best_total=out.best_total[0].cpu().numpy(),
                                             versions=out.versions[0].cpu().numpy(), qoe=out.qoe_parts[0].cpu().numpy(), scalars=sc, over=over,
                                             steps=steps)
-        return float(dev_thr[0].item())
 
     def reset(self):
         """Restarts the SAME session at chunk startup_download + 1 with an empty clock and the start-up buffer, as a freshly constructed
         reference Simulator would.  (The reference's own reset(), simulator.py:110-114, sets next_chunk = startup_download -- one chunk
         earlier than its constructor does; its environment never relies on it, it builds a new Simulator per episode.)"""
         self._sim.reset()                      # a one-entry catalogue: the next entry is this session again
+        self._sim.reset_estimator()            # and drive_client's samples belong to the session that ended
         self.next_chunk = self.startup_download + 1
         self._buffer = self.config.chunk_length * 3

@@ -22,6 +22,10 @@
 // table rows, from weights the caller brings or the predicted map.
 // The planner loop (mansy_sim_drive): those three stages and the throughput estimate between them for D decisions per session in one
 // launch, one workgroup per session, built from the device helpers the stand-alone kernels run.
+// A client's belief (mansy_sim_lookahead_client / mansy_sim_drive_client): the what-if above is an oracle (the real trace, the
+// ground-truth viewport of chunks not yet watched).  The same helpers, instantiated for a network model that divides the chunk size by
+// a throughput estimate and pointed at the predicted map, score plans as a deployable client has to; the driving kernel then keeps a
+// window of throughput samples per session and commits on the truth all the same.
 #include "mansy_kernels.h"
 #include "../../include/mansy_hip.h"
 
@@ -202,23 +206,33 @@ __global__ __launch_bounds__(256) void sim_peek_kernel(mansy_env_tables T, const
 // tile versions).  LookState is the part of the record a download moves and a QoE term reads; it lives in registers of the wave
 // that walks one candidate and is dropped at the end.
 struct LookState { double cur_time, buf_size, bwc; int cur_idx, has_prev; float prev_vq, sum; };
-struct LookConst { const double* bw; int tlen; float w0, w1, w2, max_rate; double chunk_length; };
+struct LookConst { const double* bw; int tlen; float w0, w1, w2, max_rate; double chunk_length, rate; };
+// How a virtual download takes its time: the walk over the session's real trace from where the record stands (the oracle's), or one
+// division by the bytes/s the caller believes in (a client's; the trace position of the record is then not read).
+constexpr int NET_TRACE = MANSY_SIM_NET_TRACE, NET_ESTIMATE = MANSY_SIM_NET_ESTIMATE;
 
 // One virtual step by one wavefront (lane = tile): sim_download_kernel's arithmetic from "Simulator.simulate_download" to the QoE, line
-// for line, on the tile's size / quality of the planned version and the chunk's ground-truth viewport.  qoe_row / sc_row: this step's
-// four-value output rows (nullable, launch-uniform).
+// for line, on the tile's size / quality of the planned version and the chunk's viewport map gv (ground truth or prediction).  With
+// NET_ESTIMATE the trace walk alone is replaced: download_time = chunk_size / c.rate in plain IEEE double, whatever c.rate holds.
+// qoe_row / sc_row: this step's four-value output rows (nullable, launch-uniform).
+template <int NET>
 __device__ __forceinline__ void look_step(LookState& s, const LookConst& c, int my_size, float tq, float gv, int lane, float* qoe_row,
                                           double* sc_row) {
   const int chunk_size = wave_isum(my_size);
-  const double start = s.cur_time;
-  double size = (double)chunk_size;
-  while (size > 0) {
-    const double fl = floor(s.cur_time + 1);
-    const double remain = (fl - s.cur_time) * s.bwc;
-    if (size >= remain) { s.cur_idx = s.cur_idx + 1 == c.tlen ? 0 : s.cur_idx + 1; s.bwc = c.bw[s.cur_idx]; s.cur_time = fl; size -= remain; }
-    else { s.cur_time += size / s.bwc; size = 0; }
+  double download_time;
+  if constexpr (NET == NET_TRACE) {
+    const double start = s.cur_time;
+    double size = (double)chunk_size;
+    while (size > 0) {
+      const double fl = floor(s.cur_time + 1);
+      const double remain = (fl - s.cur_time) * s.bwc;
+      if (size >= remain) { s.cur_idx = s.cur_idx + 1 == c.tlen ? 0 : s.cur_idx + 1; s.bwc = c.bw[s.cur_idx]; s.cur_time = fl; size -= remain; }
+      else { s.cur_time += size / s.bwc; size = 0; }
+    }
+    download_time = s.cur_time - start;
+  } else {
+    download_time = (double)chunk_size / c.rate;
   }
-  const double download_time = s.cur_time - start;
   double rebuf = 0.0;
   if (download_time > s.buf_size) { rebuf = download_time - s.buf_size; s.buf_size = c.chunk_length; }
   else s.buf_size = s.buf_size - download_time + c.chunk_length;
@@ -242,12 +256,14 @@ __device__ __forceinline__ void look_step(LookState& s, const LookConst& c, int 
 
 struct LookTile { int size; float quality, gv; };
 // The table values lane's tile has in virtual step t: the planned version's size and quality (a 64-lane gather over the chunk's five
-// 256 B rows) and the ground-truth map.  mrow / vrow: this lane's element of the session's NEXT chunk.
-__device__ __forceinline__ LookTile look_load(const mansy_env_tables& T, int ver, size_t mrow, size_t vrow, int t) {
+// 256 B rows) and the viewport map vmap (T.vp_gt or T.vp_pred, launch-uniform).  mrow / vrow: this lane's element of the session's
+// NEXT chunk.
+__device__ __forceinline__ LookTile look_load(const mansy_env_tables& T, const unsigned char* __restrict__ vmap, int ver, size_t mrow, size_t vrow,
+                                              int t) {
   ver = ver < 0 ? 0 : ver > NR - 1 ? NR - 1 : ver;
   const size_t m = mrow + ((size_t)t * NR + ver) * NTL;
   LookTile r;
-  r.size = T.size[m]; r.quality = T.quality[m]; r.gv = (float)T.vp_gt[vrow + (size_t)t * NTL];
+  r.size = T.size[m]; r.quality = T.quality[m]; r.gv = (float)vmap[vrow + (size_t)t * NTL];
   return r;
 }
 
@@ -269,24 +285,27 @@ struct PlanBytes { const unsigned char* p; __device__ __forceinline__ int operat
 // One candidate walked by one wavefront (lane = tile) over steps >= 1 chunks from where the session stands; returns the float32 total.
 // The loads of step t + 1 depend on t alone, not on the download of step t, so they are issued before that step's dependent chain
 // (trace walk, sequential sums) instead of behind it.  qoe_parts / scalars: the candidate's [H,4] rows (nullable, launch-uniform).
-template <typename Plan>
-__device__ __forceinline__ float look_walk(const mansy_env_tables& T, const SessionView& r, int steps, const Plan& plan, int lane, float* qoe_parts,
-                                           double* scalars) {
+// NET / rate: look_step's network model and, for NET_ESTIMATE, the session's bytes/s; vmap: the viewport table the steps are scored on.
+template <int NET, typename Plan>
+__device__ __forceinline__ float look_walk(const mansy_env_tables& T, const SessionView& r, int steps, const Plan& plan, int lane, double rate,
+                                           const unsigned char* __restrict__ vmap, float* qoe_parts, double* scalars) {
   const int chunk = r.next_chunk;
   const float* w = T.qoe_w + 3 * r.qoe;
   LookConst c;
-  c.bw = T.trace_bw + (size_t)r.trace * T.trace_len_max; c.tlen = T.trace_len[r.trace];
+  if constexpr (NET == NET_TRACE) { c.bw = T.trace_bw + (size_t)r.trace * T.trace_len_max; c.tlen = T.trace_len[r.trace]; }
+  else { c.bw = nullptr; c.tlen = 0; }
+  c.rate = rate;
   c.w0 = w[0]; c.w1 = w[1]; c.w2 = w[2]; c.max_rate = (float)T.video_rates[NR - 1]; c.chunk_length = (double)T.chunk_length;
   LookState s;
   s.cur_time = r.cur_time; s.buf_size = r.buf_size; s.cur_idx = r.cur_idx; s.has_prev = r.has_prev; s.prev_vq = r.prev_vq; s.sum = 0.f;
-  s.bwc = c.bw[s.cur_idx];
+  s.bwc = NET == NET_TRACE ? c.bw[s.cur_idx] : 0.0;
   const size_t mrow = manifest_row(T, r.video, chunk) + lane;
   const size_t vrow = viewport_cell(T, r.vp, chunk) * NTL + lane;
-  LookTile next = look_load(T, plan(0), mrow, vrow, 0);
+  LookTile next = look_load(T, vmap, plan(0), mrow, vrow, 0);
   for (int t = 0; t < steps; ++t) {
     const LookTile cur = next;
-    if (t + 1 < steps) next = look_load(T, plan(t + 1), mrow, vrow, t + 1);
-    look_step(s, c, cur.size, cur.quality, cur.gv, lane, qoe_parts ? qoe_parts + t * 4 : nullptr, scalars ? scalars + t * 4 : nullptr);
+    if (t + 1 < steps) next = look_load(T, vmap, plan(t + 1), mrow, vrow, t + 1);
+    look_step<NET>(s, c, cur.size, cur.quality, cur.gv, lane, qoe_parts ? qoe_parts + t * 4 : nullptr, scalars ? scalars + t * 4 : nullptr);
   }
   return s.sum;
 }
@@ -294,8 +313,12 @@ __device__ __forceinline__ float look_walk(const mansy_env_tables& T, const Sess
 // One wavefront per (session, candidate), lane = tile, looping over the horizon.  The K candidates of a session read the same table
 // rows; they meet in the caches.  A form that staged the rows of the horizon in LDS once per (session, 16 candidates) was measured and
 // was not faster beyond the run-to-run spread, so this plain form is the only one.
+// NET_TRACE with vmap = T.vp_gt is mansy_sim_lookahead; throughput (f64 [n]) is read by NET_ESTIMATE alone.
+template <int NET>
 __global__ __launch_bounds__(256) void sim_lookahead_kernel(mansy_env_tables T, const EnvState* __restrict__ st, int n, const int* __restrict__ plans,
-                                                            int K, int H, float* qoe_parts, double* scalars, float* total, int* steps_out) {
+                                                            int K, int H, const double* __restrict__ throughput,
+                                                            const unsigned char* __restrict__ vmap, float* qoe_parts, double* scalars, float* total,
+                                                            int* steps_out) {
   const long long wave = ((long long)blockIdx.x * 256 + threadIdx.x) >> 6;
   const int lane = threadIdx.x & 63;
   if (wave >= (long long)n * K) return;
@@ -312,8 +335,9 @@ __global__ __launch_bounds__(256) void sim_lookahead_kernel(mansy_env_tables T, 
   }
   if (steps == 0) { if (lane == 0) total[cand] = 0.f; return; }
   const PlanRows plan = {plans + cand * H * NTL + lane};
-  const float sum = look_walk(T, view_of(r), steps, plan, lane, qoe_parts ? qoe_parts + cand * H * 4 : nullptr,
-                              scalars ? scalars + cand * H * 4 : nullptr);
+  const double rate = NET == NET_ESTIMATE ? throughput[e] : 0.0;
+  const float sum = look_walk<NET>(T, view_of(r), steps, plan, lane, rate, vmap, qoe_parts ? qoe_parts + cand * H * 4 : nullptr,
+                                   scalars ? scalars + cand * H * 4 : nullptr);
   if (lane == 0) total[cand] = sum;
 }
 
@@ -530,22 +554,49 @@ struct DriveShared {
   unsigned char rec_win[MANSY_SIM_MAX_HORIZON][NTL * (NR - 1)];
 };
 constexpr int DRIVE_WIDE_SESSIONS = 256;   // up to one session per CU of an MI355X: the wide workgroup
+// The client's loop (mansy_sim_drive_client) keeps the session's throughput samples beside the record: the newest at index 7.
+struct DriveSharedClient : DriveShared { double history[MANSY_SIM_EST_MAX_WINDOW]; int count; };
+struct DriveOracle { using Shared = DriveShared; static constexpr bool client = false; };
+struct DriveClient { using Shared = DriveSharedClient; static constexpr bool client = true; };
 
-template <int WAVES>
+// The estimator of mansy_sim_drive_client after a committed step with download_time > 0, by ONE lane on the slots in LDS: the slots
+// shift down by one, the sample goes in at the top, and the estimate is the harmonic mean of the newest min(window, count) samples,
+// summed oldest first (the sample itself for one).  Returns the estimate.
+__device__ __forceinline__ double estimate_push(double* history, int& count, double sample, int window) {
+  constexpr int W = MANSY_SIM_EST_MAX_WINDOW;
+  for (int j = 0; j < W - 1; ++j) history[j] = history[j + 1];
+  history[W - 1] = sample;
+  count = count + 1 < W ? count + 1 : W;
+  const int m = window < count ? window : count;
+  if (m == 1) return sample;
+  double sum = 1.0 / history[W - m];
+  for (int j = W - m + 1; j < W; ++j) sum = sum + 1.0 / history[j];
+  return (double)m / sum;
+}
+
+// Model::client == false is mansy_sim_drive: the look-ahead on the trace and the ground truth, the last sample as the estimate; the
+// arguments from `network` on are not read.  true: the look-ahead scores on vmap with the network model `network`, and the estimate
+// comes from the window of samples (history f64 [n,8], count i32 [n], in and out).
+template <int WAVES, typename Model>
 __global__ __launch_bounds__(WAVES * 64) void sim_drive_kernel(mansy_env_tables T, EnvState* st, const double* __restrict__ fractions, int K, int H, int D,
                                                                double* throughput, int* best, float* best_total, int* versions, float* qoe_parts,
-                                                               double* scalars, unsigned char* over_out, int auto_reset) {
+                                                               double* scalars, unsigned char* over_out, int auto_reset, int network,
+                                                               const unsigned char* __restrict__ vmap, int window, double* history, int* count) {
   extern __shared__ __align__(16) unsigned char drive_lds[];
-  __shared__ DriveShared sh;
+  __shared__ typename Model::Shared sh;
   float* totals = (float*)drive_lds;
   unsigned char* plans = drive_lds + sizeof(float) * K;
   const int e = blockIdx.x, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-  bool moved = false;                         // wave 0's alone
+  bool moved = false, sampled = false;        // wave 0's alone
   if (wave == 0) {
     EnvRegs s;
     load_state(s, st[e], lane);
     store_state(sh.rec, s, lane);
     if (lane == 0) sh.throughput = throughput[e];
+    if constexpr (Model::client) {
+      if (lane < MANSY_SIM_EST_MAX_WINDOW) sh.history[lane] = history[(size_t)e * MANSY_SIM_EST_MAX_WINDOW + lane];
+      if (lane == 0) { const int c = count[e]; sh.count = c < 0 ? 0 : c > MANSY_SIM_EST_MAX_WINDOW ? MANSY_SIM_EST_MAX_WINDOW : c; }
+    }
   }
   __syncthreads();
   for (int d = 0; d < D; ++d) {
@@ -587,7 +638,13 @@ __global__ __launch_bounds__(WAVES * 64) void sim_drive_kernel(mansy_env_tables 
     if (steps > 0) {
       for (int k = wave; k < K; k += WAVES) {
         const PlanBytes plan = {plans + k * H * NTL + lane};
-        const float sum = look_walk(T, v, steps, plan, lane, nullptr, nullptr);
+        float sum;
+        if constexpr (Model::client) {         // (network is a kernel argument: the whole workgroup takes the same side)
+          sum = network == NET_ESTIMATE ? look_walk<NET_ESTIMATE>(T, v, steps, plan, lane, thr, vmap, nullptr, nullptr)
+                                        : look_walk<NET_TRACE>(T, v, steps, plan, lane, 0.0, vmap, nullptr, nullptr);
+        } else {
+          sum = look_walk<NET_TRACE>(T, v, steps, plan, lane, 0.0, T.vp_gt, nullptr, nullptr);
+        }
         if (lane == 0) totals[k] = sum;
       }
     }
@@ -615,7 +672,18 @@ __global__ __launch_bounds__(WAVES * 64) void sim_drive_kernel(mansy_env_tables 
         const Committed c = sim_commit(T, s, ver, lane, nullptr, nullptr, nullptr, scalars ? scalars + 4 * row : nullptr,
                                        qoe_parts ? qoe_parts + 4 * row : nullptr, over_out + row, auto_reset);
         store_state(sh.rec, s, lane);
-        if (lane == 0) sh.throughput = c.download_time > 0 ? (double)c.chunk_size / c.download_time : thr;
+        if constexpr (Model::client) {
+          if (c.download_time > 0) {           // (wave-uniform)
+            if (lane == 0) {
+              int cnt = sh.count;
+              sh.throughput = estimate_push(sh.history, cnt, (double)c.chunk_size / c.download_time, window);
+              sh.count = cnt;
+            }
+            sampled = true;
+          }
+        } else {
+          if (lane == 0) sh.throughput = c.download_time > 0 ? (double)c.chunk_size / c.download_time : thr;
+        }
         moved = true;
       }
     }
@@ -628,6 +696,12 @@ __global__ __launch_bounds__(WAVES * 64) void sim_drive_kernel(mansy_env_tables 
       store_state(st[e], s, lane);
     }
     if (lane == 0) throughput[e] = sh.throughput;
+    if constexpr (Model::client) {
+      if (sampled) {                          // the slots and the count go back once, if a step gave a sample
+        if (lane < MANSY_SIM_EST_MAX_WINDOW) history[(size_t)e * MANSY_SIM_EST_MAX_WINDOW + lane] = sh.history[lane];
+        if (lane == 0) count[e] = sh.count;
+      }
+    }
   }
 }
 
@@ -678,8 +752,35 @@ int mansy_sim_lookahead(const mansy_env_tables* T, const void* state, int n, con
   MANSY_REQUIRE(K >= 1 && K <= MANSY_SIM_MAX_CANDIDATES, "sim_lookahead: K must be in [1, %d]", MANSY_SIM_MAX_CANDIDATES);
   MANSY_REQUIRE(H >= 1 && H <= MANSY_SIM_MAX_HORIZON, "sim_lookahead: H must be in [1, %d]", MANSY_SIM_MAX_HORIZON);
   MANSY_REQUIRE((long long)n * K < (1ll << 31), "sim_lookahead: n * K must be below 2^31");
-  MANSY_LAUNCH(sim_lookahead_kernel, dim3((unsigned)mansy_ceil_div((long long)n * K * 64, 256)), dim3(256), 0, (hipStream_t)stream, *T,
-               (const EnvState*)state, n, plans, K, H, qoe_parts, scalars, total, steps);
+  MANSY_LAUNCH(sim_lookahead_kernel<NET_TRACE>, dim3((unsigned)mansy_ceil_div((long long)n * K * 64, 256)), dim3(256), 0, (hipStream_t)stream, *T,
+               (const EnvState*)state, n, plans, K, H, (const double*)nullptr, T->vp_gt, qoe_parts, scalars, total, steps);
+  if (best || best_total)
+    MANSY_LAUNCH(sim_best_kernel, dim3(mansy_ceil_div((long long)n * 64, 256)), dim3(256), 0, (hipStream_t)stream, total, n, K, best, best_total);
+  MANSY_LAUNCH_CHECK();
+  return MANSY_OK;
+}
+
+int mansy_sim_lookahead_client(const mansy_env_tables* T, const void* state, int n, const int* plans, int K, int H, const double* throughput,
+                               int viewport, float* qoe_parts, double* scalars, float* total, int* steps, int* best, float* best_total,
+                               void* stream) {
+  int rc = check_sim_tables(T, "sim_lookahead_client"); if (rc) return rc;
+  MANSY_REQUIRE(state, "sim_lookahead_client: null state");
+  MANSY_REQUIRE(plans, "sim_lookahead_client: null plans");
+  MANSY_REQUIRE(total, "sim_lookahead_client: null total");
+  MANSY_REQUIRE(steps, "sim_lookahead_client: null steps");
+  MANSY_REQUIRE(n >= 1, "sim_lookahead_client: n must be >= 1");
+  MANSY_REQUIRE(K >= 1 && K <= MANSY_SIM_MAX_CANDIDATES, "sim_lookahead_client: K must be in [1, %d]", MANSY_SIM_MAX_CANDIDATES);
+  MANSY_REQUIRE(H >= 1 && H <= MANSY_SIM_MAX_HORIZON, "sim_lookahead_client: H must be in [1, %d]", MANSY_SIM_MAX_HORIZON);
+  MANSY_REQUIRE((long long)n * K < (1ll << 31), "sim_lookahead_client: n * K must be below 2^31");
+  MANSY_REQUIRE(viewport == MANSY_SIM_VIEW_GT || viewport == MANSY_SIM_VIEW_PRED, "sim_lookahead_client: viewport must be MANSY_SIM_VIEW_GT (0) or MANSY_SIM_VIEW_PRED (1)");
+  const unsigned char* vmap = viewport == MANSY_SIM_VIEW_PRED ? T->vp_pred : T->vp_gt;
+  const dim3 grid((unsigned)mansy_ceil_div((long long)n * K * 64, 256));
+  if (throughput)
+    MANSY_LAUNCH(sim_lookahead_kernel<NET_ESTIMATE>, grid, dim3(256), 0, (hipStream_t)stream, *T, (const EnvState*)state, n, plans, K, H, throughput, vmap,
+                 qoe_parts, scalars, total, steps);
+  else
+    MANSY_LAUNCH(sim_lookahead_kernel<NET_TRACE>, grid, dim3(256), 0, (hipStream_t)stream, *T, (const EnvState*)state, n, plans, K, H, throughput, vmap,
+                 qoe_parts, scalars, total, steps);
   if (best || best_total)
     MANSY_LAUNCH(sim_best_kernel, dim3(mansy_ceil_div((long long)n * 64, 256)), dim3(256), 0, (hipStream_t)stream, total, n, K, best, best_total);
   MANSY_LAUNCH_CHECK();
@@ -718,11 +819,40 @@ int mansy_sim_drive(const mansy_env_tables* T, void* state, int n, const double*
   // few sessions: sixteen waves each, so that every CU works on the one session it holds; many: four, so that a CU holds several
   // sessions whose serial parts (the leading allocations, the commit) overlap (DESIGN.md section 1 has the measurement)
   if (n <= DRIVE_WIDE_SESSIONS)
-    MANSY_LAUNCH(sim_drive_kernel<16>, dim3((unsigned)n), dim3(16 * 64), lds, (hipStream_t)stream, *T, (EnvState*)state, fractions, K, H, D, throughput,
-                 best, best_total, versions, qoe_parts, scalars, over, auto_reset);
+    MANSY_LAUNCH((sim_drive_kernel<16, DriveOracle>), dim3((unsigned)n), dim3(16 * 64), lds, (hipStream_t)stream, *T, (EnvState*)state, fractions, K, H, D,
+                 throughput, best, best_total, versions, qoe_parts, scalars, over, auto_reset, NET_TRACE, T->vp_gt, 1, (double*)nullptr, (int*)nullptr);
   else
-    MANSY_LAUNCH(sim_drive_kernel<4>, dim3((unsigned)n), dim3(4 * 64), lds, (hipStream_t)stream, *T, (EnvState*)state, fractions, K, H, D, throughput,
-                 best, best_total, versions, qoe_parts, scalars, over, auto_reset);
+    MANSY_LAUNCH((sim_drive_kernel<4, DriveOracle>), dim3((unsigned)n), dim3(4 * 64), lds, (hipStream_t)stream, *T, (EnvState*)state, fractions, K, H, D,
+                 throughput, best, best_total, versions, qoe_parts, scalars, over, auto_reset, NET_TRACE, T->vp_gt, 1, (double*)nullptr, (int*)nullptr);
+  MANSY_LAUNCH_CHECK();
+  return MANSY_OK;
+}
+
+int mansy_sim_drive_client(const mansy_env_tables* T, void* state, int n, const double* fractions, int K, int H, int D, double* throughput,
+                           int network, int viewport, int window, double* history, int* count, int* best, float* best_total, int* versions,
+                           float* qoe_parts, double* scalars, unsigned char* over, int auto_reset, void* stream) {
+  int rc = check_sim_tables(T, "sim_drive_client"); if (rc) return rc;
+  MANSY_REQUIRE(state, "sim_drive_client: null state");
+  MANSY_REQUIRE(fractions, "sim_drive_client: null fractions");
+  MANSY_REQUIRE(throughput, "sim_drive_client: null throughput");
+  MANSY_REQUIRE(history, "sim_drive_client: null history");
+  MANSY_REQUIRE(count, "sim_drive_client: null count");
+  MANSY_REQUIRE(over, "sim_drive_client: null over");
+  MANSY_REQUIRE(n >= 1, "sim_drive_client: n must be >= 1");
+  MANSY_REQUIRE(K >= 1 && K <= MANSY_SIM_DRIVE_MAX_CANDIDATES, "sim_drive_client: K must be in [1, %d]", MANSY_SIM_DRIVE_MAX_CANDIDATES);
+  MANSY_REQUIRE(H >= 1 && H <= MANSY_SIM_MAX_HORIZON, "sim_drive_client: H must be in [1, %d]", MANSY_SIM_MAX_HORIZON);
+  MANSY_REQUIRE(D >= 1 && D <= MANSY_SIM_DRIVE_MAX_DECISIONS, "sim_drive_client: D must be in [1, %d]", MANSY_SIM_DRIVE_MAX_DECISIONS);
+  MANSY_REQUIRE(network == MANSY_SIM_NET_TRACE || network == MANSY_SIM_NET_ESTIMATE, "sim_drive_client: network must be MANSY_SIM_NET_TRACE (0) or MANSY_SIM_NET_ESTIMATE (1)");
+  MANSY_REQUIRE(viewport == MANSY_SIM_VIEW_GT || viewport == MANSY_SIM_VIEW_PRED, "sim_drive_client: viewport must be MANSY_SIM_VIEW_GT (0) or MANSY_SIM_VIEW_PRED (1)");
+  MANSY_REQUIRE(window >= 1 && window <= MANSY_SIM_EST_MAX_WINDOW, "sim_drive_client: window must be in [1, %d]", MANSY_SIM_EST_MAX_WINDOW);
+  const unsigned char* vmap = viewport == MANSY_SIM_VIEW_PRED ? T->vp_pred : T->vp_gt;
+  const size_t lds = sizeof(float) * K + (size_t)K * H * NTL;      // as mansy_sim_drive's, and the same two workgroup widths
+  if (n <= DRIVE_WIDE_SESSIONS)
+    MANSY_LAUNCH((sim_drive_kernel<16, DriveClient>), dim3((unsigned)n), dim3(16 * 64), lds, (hipStream_t)stream, *T, (EnvState*)state, fractions, K, H, D,
+                 throughput, best, best_total, versions, qoe_parts, scalars, over, auto_reset, network, vmap, window, history, count);
+  else
+    MANSY_LAUNCH((sim_drive_kernel<4, DriveClient>), dim3((unsigned)n), dim3(4 * 64), lds, (hipStream_t)stream, *T, (EnvState*)state, fractions, K, H, D,
+                 throughput, best, best_total, versions, qoe_parts, scalars, over, auto_reset, network, vmap, window, history, count);
   MANSY_LAUNCH_CHECK();
   return MANSY_OK;
 }
