@@ -9,6 +9,7 @@
 // These blocks (<= 16x16x64) cannot fill an MFMA tile; the kernel is HBM/latency-bound and its
 // job is coalesced 256-byte row reads and zero extra traffic.
 #include "mansy_kernels.h"
+#include <type_traits>
 
 namespace {
 
@@ -20,23 +21,23 @@ struct AttnPtrs {
   const float* Q; const float* K; const float* V; float* O; float* P;
   const float* dO; float* dQ; float* dK; float* dV;
   float* dS_out; float* Pk_out;     // q1x4 backward, deferred dK/dV: [nb*H, Lk] score gradients / dropped probabilities
-  // bf16 images of the OUTPUT rows (bf16-storage mode, round 6; 4-heads-per-wave kernels only): the float4 stored at address a also goes, rounded, to
-  // img_s + (a - img_f) -- one mapping for O / dQ / dK / dV (they are rows of one slab).  Null: no image.
-  const float* img_f; unsigned short* img_s;
-  int img_only;                     // != 0 (with img_s): the rows are operands of dense products and nothing else -- the float4 store is skipped
-  int kv16;                         // != 0 (with img_s; q1x4 kernels): the K / V rows (and the pull form's Q rows) are READ from their bf16 images -- the
-                                    // K/V cache of the bf16-storage mode is bf16 in HBM (written by the projection's epilogue): half the cache traffic
+  AttnImage img;                    // bf16 images (4-heads-per-wave kernels only; mansy_kernels.h), `only` / `kv16` cleared without an image
 };
 // a 4-float piece of a K / V / Q row: from the float slab, or (kv16) from its bf16 image at the same element index
-__device__ __forceinline__ float4 attn_ld4(const AttnPtrs& p, const float* addr) {
-  if (p.kv16) {
-    const mansy_bf16x4 t = *reinterpret_cast<const mansy_bf16x4*>(p.img_s + (addr - p.img_f));
+__device__ __forceinline__ float4 attn_ld4(const AttnImage& img, const float* addr) {
+  if (img.kv16) {
+    const mansy_bf16x4 t = *reinterpret_cast<const mansy_bf16x4*>(img.s + (addr - img.f));
     return make_float4((float)t[0], (float)t[1], (float)t[2], (float)t[3]);
   }
   return *reinterpret_cast<const float4*>(addr);
 }
-#define ATTN_ST(p, addr, v) do { if (!(p).img_only) *reinterpret_cast<float4*>(addr) = (v); ATTN_IMG(p, addr, v); } while (0)
-#define ATTN_IMG(p, addr, v) do { if ((p).img_s) mansy_st_bf16x4((p).img_s + ((addr) - (p).img_f), (v).x, (v).y, (v).z, (v).w); } while (0)
+// a 4-float piece of an output row: to the float slab (unless the image is all that is wanted) and, rounded, to its image
+#define ATTN_ST(img, addr, v) do { if (!(img).only) *reinterpret_cast<float4*>(addr) = (v); ATTN_IMG(img, addr, v); } while (0)
+#define ATTN_IMG(img, addr, v) do { if ((img).s) mansy_st_bf16x4((img).s + ((addr) - (img).f), (v).x, (v).y, (v).z, (v).w); } while (0)
+
+// dropout of the attention probabilities: element idx of the site is kept with probability 1 - p and scaled by ds = 1 / (1 - p)
+__device__ __forceinline__ float drop_scale(const MansyDrop& drop) { return drop.p > 0.f ? 1.f / (1.f - drop.p) : 1.f; }
+__device__ __forceinline__ bool kept(const MansyDrop& drop, long long idx) { return mansy_keep(drop.seed, drop.site, drop.base + (uint32_t)idx, drop.p); }
 
 __device__ __forceinline__ void load_rows(const float* base, long long rs, int L, int dh, int lane, float* lds) {
   for (int i = 0; i < L; ++i)
@@ -77,12 +78,12 @@ __global__ __launch_bounds__(64 * WAVES) void attn_fwd_kernel(AttnPtrs p, AttnSh
     float sum = 0.f;
     for (int j = 0; j < Lk; ++j) { const float e = expf(p_l[i * (LMAX + 1) + j] - m); p_l[i * (LMAX + 1) + j] = e; sum += e; }
     const float inv = 1.f / sum;
-    const float ds = drop.p > 0.f ? 1.f / (1.f - drop.p) : 1.f;
+    const float ds = drop.p > 0.f ? 1.f / (1.f - drop.p) : 1.f;      // (drop_scale written out: through the helper hipcc tests drop.p once more per row)
     for (int j = 0; j < Lk; ++j) {
       float pv = p_l[i * (LMAX + 1) + j] * inv;
       const long long pidx = (bh * Lq + i) * Lk + j;
       if (p.P) p.P[pidx] = pv;
-      if (drop.p > 0.f) pv = mansy_keep(drop.seed, drop.site, drop.base + (uint32_t)pidx, drop.p) ? pv * ds : 0.f;
+      if (drop.p > 0.f) pv = kept(drop, pidx) ? pv * ds : 0.f;
       p_l[i * (LMAX + 1) + j] = pv;
     }
   }
@@ -116,7 +117,7 @@ __global__ __launch_bounds__(64 * WAVES) void attn_bwd_kernel(AttnPtrs p, AttnSh
   const float* Vb = p.V + b * s.v_bs + h * dh;
   const float* dOb = p.dO + b * s.o_bs + h * dh;
   float* do_l = sA[wave]; float* v_l = sB[wave]; float* p_l = sP[wave]; float* d_l = sD[wave];
-  const float ds = drop.p > 0.f ? 1.f / (1.f - drop.p) : 1.f;
+  const float ds = drop_scale(drop);
   if (active) {
     load_rows(dOb, s.o_rs, Lq, dh, lane, do_l);
     load_rows(Vb, s.v_rs, Lk, dh, lane, v_l);
@@ -126,7 +127,7 @@ __global__ __launch_bounds__(64 * WAVES) void attn_bwd_kernel(AttnPtrs p, AttnSh
       const float pv = p.P[pidx];
       p_l[i * (LMAX + 1) + j] = pv;
       float keepf = 1.f;
-      if (drop.p > 0.f) keepf = mansy_keep(drop.seed, drop.site, drop.base + (uint32_t)pidx, drop.p) ? ds : 0.f;
+      if (drop.p > 0.f) keepf = kept(drop, pidx) ? ds : 0.f;
       d_l[i * (LMAX + 1) + j] = pv * keepf;    // dropped probabilities (for dV)
     }
   }
@@ -149,7 +150,7 @@ __global__ __launch_bounds__(64 * WAVES) void attn_bwd_kernel(AttnPtrs p, AttnSh
       float acc = 0.f;
       for (int d = 0; d < dh; ++d) acc = fmaf(do_l[i * DH_LD + d], v_l[j * DH_LD + d], acc);
       float keepf = 1.f;
-      if (drop.p > 0.f) keepf = mansy_keep(drop.seed, drop.site, drop.base + (uint32_t)((bh * Lq + i) * Lk + j), drop.p) ? ds : 0.f;
+      if (drop.p > 0.f) keepf = kept(drop, (bh * Lq + i) * Lk + j) ? ds : 0.f;
       d_l[i * (LMAX + 1) + j] = acc * keepf;   // dP (wrt pre-dropout probabilities)
     }
   }
@@ -217,7 +218,7 @@ __global__ __launch_bounds__(64 * WAVES) void attn_fwd_q1_kernel(AttnPtrs p, Att
 #pragma unroll
   for (int j = 0; j < LMAX; ++j) if (j < Lk) { sc[j] = expf(sc[j] - m); sum += sc[j]; }
   const float inv = 1.f / sum;
-  const float ds = drop.p > 0.f ? 1.f / (1.f - drop.p) : 1.f;
+  const float ds = drop_scale(drop);
   float o = 0.f;
 #pragma unroll
   for (int j = 0; j < LMAX; ++j) {
@@ -225,7 +226,7 @@ __global__ __launch_bounds__(64 * WAVES) void attn_fwd_q1_kernel(AttnPtrs p, Att
       float pv = sc[j] * inv;
       const long long pidx = bh * Lk + j;
       if (p.P && lane == j) p.P[pidx] = pv;
-      if (drop.p > 0.f) pv = mansy_keep(drop.seed, drop.site, drop.base + (uint32_t)pidx, drop.p) ? pv * ds : 0.f;
+      if (drop.p > 0.f) pv = kept(drop, pidx) ? pv * ds : 0.f;
       o = fmaf(pv, v[j], o);
     }
   }
@@ -245,7 +246,7 @@ __global__ __launch_bounds__(64 * WAVES) void attn_bwd_q1_kernel(AttnPtrs p, Att
   float* dVb = p.dV + b * s.v_bs + h * dh + lane;
   const float q = on ? p.Q[b * s.q_bs + h * dh + lane] : 0.f;
   const float dO = on ? p.dO[b * s.o_bs + h * dh + lane] : 0.f;
-  const float ds = drop.p > 0.f ? 1.f / (1.f - drop.p) : 1.f;
+  const float ds = drop_scale(drop);
   float k[LMAX], dP[LMAX], P[LMAX], keepf[LMAX], dk_old[LMAX], dv_old[LMAX];
 #pragma unroll
   for (int j = 0; j < LMAX; ++j) {
@@ -257,7 +258,7 @@ __global__ __launch_bounds__(64 * WAVES) void attn_bwd_q1_kernel(AttnPtrs p, Att
     dP[j] = dO * vj;
     P[j] = j < Lk ? p.P[bh * Lk + j] : 0.f;
     keepf[j] = 1.f;
-    if (drop.p > 0.f && j < Lk) keepf[j] = mansy_keep(drop.seed, drop.site, drop.base + (uint32_t)(bh * Lk + j), drop.p) ? ds : 0.f;
+    if (drop.p > 0.f && j < Lk) keepf[j] = kept(drop, bh * Lk + j) ? ds : 0.f;
   }
   float delta = 0.f;
 #pragma unroll
@@ -279,35 +280,54 @@ __global__ __launch_bounds__(64 * WAVES) void attn_bwd_q1_kernel(AttnPtrs p, Att
   if (on) p.dQ[b * s.q_bs + h * dh + lane] = dq;
 }
 
-// ---- Lq == 1, dh == 64, H % 4 == 0: FOUR heads per wave, 16 lanes x float4 per head.  A (batch, 4-head) group is 1 KiB of
+// ---- Lq == 1 or Lq == Lk <= 10, dh == 64, H % 4 == 0: FOUR heads per wave, 16 lanes x float4 per head.  A (batch, 4-head) group is 1 KiB of
 // contiguous q/k/v, so every load/store is a full-width 16-B-per-lane instruction (4x fewer memory instructions and waves
 // than one head per wave) and the score reductions stay inside 16-lane groups (4 shuffle steps).
+// wave -> (batch b, head h of the wave's 4-head group); lane c of the head's 16 owns the floats col .. col + 3 of a row;
+// gbase = first lane of the head's group (shuffle source base), bh = the head's row in the [nb * H, ...] coefficient arrays
+struct Wave4 {
+  int b, h, c, gbase, Lk, col; long long bh, nbh;      // Lk = s.Lk, the key rows; nbh = nb * H, the rows of the coefficient arrays
+  template <class T> __device__ __forceinline__ T* rows(T* slab, long long bs) const { return slab + b * bs + col; }      // this lane's piece of the group's first row
+};
+// declares the wave's Wave4 `w`; a wave of the last workgroup without a group returns from the kernel.  A macro, not a function: hipcc optimises a helper
+// function on its own before it inlines it, and the kernels then come out scheduled differently.
+#define WAVE4_OR_RETURN(w, s)                                                                                               \
+  Wave4 w;                                                                                                                  \
+  {                                                                                                                         \
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;                                                             \
+    const int hg = (s).H >> 2; /* head groups per batch entry */                                                            \
+    const long long g = (long long)blockIdx.x * WAVES + wave;                                                               \
+    if (g >= (long long)(s).nb * hg) return;                                                                                \
+    w.b = (int)(g / hg); w.h = (int)(g % hg) * 4 + (lane >> 4); w.c = lane & 15; w.gbase = lane & 48;                       \
+    w.bh = (long long)w.b * (s).H + w.h; w.nbh = (long long)(s).nb * (s).H;                                                 \
+    w.Lk = (s).Lk;                                                                                                          \
+    w.col = w.h * 64 + w.c * 4;                                                                                             \
+  }
 __device__ __forceinline__ float group16_sum(float v) { return row16_sum(v); }
 __device__ __forceinline__ float dot4(const float4& a, const float4& b) { return (a.x * b.x + a.y * b.y) + (a.z * b.z + a.w * b.w); }
+__device__ __forceinline__ float4 mul4(float a, const float4& v) { return make_float4(a * v.x, a * v.y, a * v.z, a * v.w); }
+__device__ __forceinline__ float4 fma4(float a, const float4& v, const float4& acc) {
+  return make_float4(fmaf(a, v.x, acc.x), fmaf(a, v.y, acc.y), fmaf(a, v.z, acc.z), fmaf(a, v.w, acc.w));
+}
 
+// ---- Lq == 1 on the 4-heads-per-wave layout.
 // LKT = compile-time bound on the key rows (>= s.Lk): every K / V / P load of a wave is issued up front, unconditionally
 // (rows >= Lk re-read row Lk-1 and are masked out of the arithmetic).  With a runtime `if (j < Lk)` around each load hipcc
 // branches and waits per row: Lk dependent HBM round trips per wave, 3.5 us per cached step in the decode loop.
 template <int LKT>
 __global__ __launch_bounds__(64 * WAVES) void attn_fwd_q1x4_kernel(AttnPtrs p, AttnShape s, MansyDrop drop) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int hg = s.H >> 2;                                  // head groups per batch entry
-  const long long g = (long long)blockIdx.x * WAVES + wave;
-  if (g >= (long long)s.nb * hg) return;
-  const int b = (int)(g / hg), h = (int)(g % hg) * 4 + (lane >> 4), c = lane & 15;
-  const long long bh = (long long)b * s.H + h;
-  const int Lk = s.Lk;
-  const int col = h * 64 + c * 4;
-  const float4 q = *reinterpret_cast<const float4*>(p.Q + b * s.q_bs + col);
-  const float* Kb = p.K + b * s.k_bs + col;
-  const float* Vb = p.V + b * s.v_bs + col;
+  WAVE4_OR_RETURN(w, s);
+  const int Lk = w.Lk;
+  const float4 q = *reinterpret_cast<const float4*>(w.rows(p.Q, s.q_bs));
+  const float* Kb = w.rows(p.K, s.k_bs);
+  const float* Vb = w.rows(p.V, s.v_bs);
   float sc[LKT];
   float4 k[LKT], v[LKT];
 #pragma unroll
   for (int j = 0; j < LKT; ++j) {
     const int jc = min(j, Lk - 1);
-    k[j] = attn_ld4(p, Kb + jc * s.k_rs);
-    v[j] = attn_ld4(p, Vb + jc * s.v_rs);
+    k[j] = attn_ld4(p.img, Kb + jc * s.k_rs);
+    v[j] = attn_ld4(p.img, Vb + jc * s.v_rs);
   }
   float m = -INFINITY;
 #pragma unroll
@@ -319,50 +339,45 @@ __global__ __launch_bounds__(64 * WAVES) void attn_fwd_q1x4_kernel(AttnPtrs p, A
 #pragma unroll
   for (int j = 0; j < LKT; ++j) { sc[j] = j < Lk ? expf(sc[j] - m) : 0.f; sum += sc[j]; }
   const float inv = 1.f / sum;
-  const float ds = drop.p > 0.f ? 1.f / (1.f - drop.p) : 1.f;
+  const float ds = drop_scale(drop);
   float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
   for (int j = 0; j < LKT; ++j) {
     float pv = sc[j] * inv;                      // 0 for j >= Lk
-    const long long pidx = bh * Lk + j;
-    if (p.P && c == j && j < Lk) p.P[pidx] = pv;
-    if (drop.p > 0.f) pv = mansy_keep(drop.seed, drop.site, drop.base + (uint32_t)pidx, drop.p) ? pv * ds : 0.f;
-    o.x = fmaf(pv, v[j].x, o.x); o.y = fmaf(pv, v[j].y, o.y); o.z = fmaf(pv, v[j].z, o.z); o.w = fmaf(pv, v[j].w, o.w);
+    const long long pidx = w.bh * Lk + j;
+    if (p.P && w.c == j && j < Lk) p.P[pidx] = pv;
+    if (drop.p > 0.f) pv = kept(drop, pidx) ? pv * ds : 0.f;
+    o = fma4(pv, v[j], o);
   }
-  ATTN_ST(p, p.O + b * s.o_bs + col, o);
+  ATTN_ST(p.img, w.rows(p.O, s.o_bs), o);
 }
 
 template <int LKT>
 __global__ __launch_bounds__(64 * WAVES) void attn_bwd_q1x4_kernel(AttnPtrs p, AttnShape s, MansyDrop drop, int accum_kv) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int hg = s.H >> 2;
-  const long long g = (long long)blockIdx.x * WAVES + wave;
-  if (g >= (long long)s.nb * hg) return;
-  const int b = (int)(g / hg), h = (int)(g % hg) * 4 + (lane >> 4);
-  const long long bh = (long long)b * s.H + h;
-  const int Lk = s.Lk;
-  const int col = h * 64 + (lane & 15) * 4;
-  const float4 q = *reinterpret_cast<const float4*>(p.Q + b * s.q_bs + col);
-  const float4 dO = *reinterpret_cast<const float4*>(p.dO + b * s.o_bs + col);
-  const float* Kb = p.K + b * s.k_bs + col;
-  const float* Vb = p.V + b * s.v_bs + col;
-  float* dKb = p.dK + b * s.k_bs + col;
-  float* dVb = p.dV + b * s.v_bs + col;
-  const float ds = drop.p > 0.f ? 1.f / (1.f - drop.p) : 1.f;
+  WAVE4_OR_RETURN(w, s);
+  const long long bh = w.bh;
+  const int Lk = w.Lk;
+  const float4 q = *reinterpret_cast<const float4*>(w.rows(p.Q, s.q_bs));
+  const float4 dO = *reinterpret_cast<const float4*>(w.rows(p.dO, s.o_bs));
+  const float* Kb = w.rows(p.K, s.k_bs);
+  const float* Vb = w.rows(p.V, s.v_bs);
+  float* dKb = w.rows(p.dK, s.k_bs);
+  float* dVb = w.rows(p.dV, s.v_bs);
+  const float ds = drop_scale(drop);
   float4 k[LKT], vv[LKT];
   float dP[LKT], P[LKT], keepf[LKT];
 #pragma unroll
   for (int j = 0; j < LKT; ++j) {
     const int jc = min(j, Lk - 1);
-    k[j] = attn_ld4(p, Kb + jc * s.k_rs);
-    vv[j] = attn_ld4(p, Vb + jc * s.v_rs);
+    k[j] = attn_ld4(p.img, Kb + jc * s.k_rs);
+    vv[j] = attn_ld4(p.img, Vb + jc * s.v_rs);
     P[j] = p.P[bh * Lk + jc];
   }
   float delta = 0.f;
 #pragma unroll
   for (int j = 0; j < LKT; ++j) {
     keepf[j] = 1.f;
-    if (drop.p > 0.f) keepf[j] = mansy_keep(drop.seed, drop.site, drop.base + (uint32_t)(bh * Lk + j), drop.p) ? ds : 0.f;
+    if (drop.p > 0.f) keepf[j] = kept(drop, bh * Lk + j) ? ds : 0.f;
     if (j >= Lk) P[j] = 0.f;
     dP[j] = group16_sum(dot4(dO, vv[j])) * keepf[j];
     delta = fmaf(P[j], dP[j], delta);
@@ -372,14 +387,13 @@ __global__ __launch_bounds__(64 * WAVES) void attn_bwd_q1x4_kernel(AttnPtrs p, A
 #pragma unroll
   for (int j = 0; j < LKT; ++j) {
     dS[j] = P[j] * (dP[j] - delta) * s.scale;      // 0 for j >= Lk
-    dq.x = fmaf(dS[j], k[j].x, dq.x); dq.y = fmaf(dS[j], k[j].y, dq.y); dq.z = fmaf(dS[j], k[j].z, dq.z); dq.w = fmaf(dS[j], k[j].w, dq.w);
+    dq = fma4(dS[j], k[j], dq);
   }
-  ATTN_ST(p, p.dQ + b * s.q_bs + col, dq);
+  ATTN_ST(p.img, w.rows(p.dQ, s.q_bs), dq);
   if (p.dS_out) {          // deferred dK / dV (mansy_launch_attn_kvgrad): keep this step's coefficients, touch no K/V gradient row
-    const int c = lane & 15;
 #pragma unroll
     for (int j = 0; j < LKT; ++j) {
-      if (c == j && j < Lk) { p.dS_out[bh * Lk + j] = dS[j]; p.Pk_out[bh * Lk + j] = P[j] * keepf[j]; }
+      if (w.c == j && j < Lk) { p.dS_out[bh * Lk + j] = dS[j]; p.Pk_out[bh * Lk + j] = P[j] * keepf[j]; }
     }
     return;
   }
@@ -426,72 +440,67 @@ struct SelfPull {
 };
 template <int LKT>
 __global__ __launch_bounds__(64 * WAVES) void attn_bwd_selfpull_q1x4_kernel(AttnPtrs p, AttnShape s, MansyDrop drop, SelfPull sp) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int hg = s.H >> 2;
-  const long long g = (long long)blockIdx.x * WAVES + wave;
-  if (g >= (long long)s.nb * hg) return;
-  const int b = (int)(g / hg), h = (int)(g % hg) * 4 + (lane >> 4), c = lane & 15;
-  const long long bh = (long long)b * s.H + h, nbh = (long long)s.nb * s.H;
-  const int Lk = s.Lk;                       // == sp.step + 1
-  const int col = h * 64 + c * 4;
-  const float4 q = *reinterpret_cast<const float4*>(sp.Q_all + sp.step * sp.q_ts + b * s.q_bs + col);
-  const float4 dO = *reinterpret_cast<const float4*>(sp.dO_all + sp.step * sp.o_ts + b * s.o_bs + col);
-  const float* Kb = p.K + b * s.k_bs + col;
-  const float* Vb = p.V + b * s.v_bs + col;
-  const float ds = drop.p > 0.f ? 1.f / (1.f - drop.p) : 1.f;
+  WAVE4_OR_RETURN(w, s);
+  const long long nbh = w.nbh;
+  const int Lk = w.Lk;                       // == sp.step + 1
+  const float4 q = *reinterpret_cast<const float4*>(w.rows(sp.Q_all + sp.step * sp.q_ts, s.q_bs));
+  const float4 dO = *reinterpret_cast<const float4*>(w.rows(sp.dO_all + sp.step * sp.o_ts, s.o_bs));
+  const float* Kb = w.rows(p.K, s.k_bs);
+  const float* Vb = w.rows(p.V, s.v_bs);
+  const float ds = drop_scale(drop);
   float4 k[LKT], vv[LKT];
   float dP[LKT], P[LKT], keepf[LKT];
 #pragma unroll
   for (int j = 0; j < LKT; ++j) {
     const int jc = min(j, Lk - 1);
-    k[j] = attn_ld4(p, Kb + jc * s.k_rs);
-    vv[j] = attn_ld4(p, Vb + jc * s.v_rs);
-    P[j] = p.P[bh * Lk + jc];
+    k[j] = attn_ld4(p.img, Kb + jc * s.k_rs);
+    vv[j] = attn_ld4(p.img, Vb + jc * s.v_rs);
+    P[j] = p.P[w.bh * Lk + jc];
   }
   float delta = 0.f;
 #pragma unroll
   for (int j = 0; j < LKT; ++j) {
     keepf[j] = 1.f;
-    if (drop.p > 0.f) keepf[j] = mansy_keep(drop.seed, drop.site, drop.base + (uint32_t)(bh * Lk + j), drop.p) ? ds : 0.f;
+    if (drop.p > 0.f) keepf[j] = kept(drop, w.bh * Lk + j) ? ds : 0.f;
     if (j >= Lk) P[j] = 0.f;
     dP[j] = group16_sum(dot4(dO, vv[j])) * keepf[j];
     delta = fmaf(P[j], dP[j], delta);
   }
   float4 dq = make_float4(0.f, 0.f, 0.f, 0.f);
   float dS_own = 0.f, Pk_own = 0.f;          // coefficients (step, step): this step's term of its own K/V row
-  float* dS_row = sp.dS_all + ((long long)sp.step * nbh + bh) * sp.T;
-  float* Pk_row = sp.Pk_all + ((long long)sp.step * nbh + bh) * sp.T;
+  float* dS_row = sp.dS_all + ((long long)sp.step * nbh + w.bh) * sp.T;
+  float* Pk_row = sp.Pk_all + ((long long)sp.step * nbh + w.bh) * sp.T;
 #pragma unroll
   for (int j = 0; j < LKT; ++j) {
     const float dSj = P[j] * (dP[j] - delta) * s.scale;      // 0 for j >= Lk
     const float Pkj = P[j] * keepf[j];
-    dq.x = fmaf(dSj, k[j].x, dq.x); dq.y = fmaf(dSj, k[j].y, dq.y); dq.z = fmaf(dSj, k[j].z, dq.z); dq.w = fmaf(dSj, k[j].w, dq.w);
+    dq = fma4(dSj, k[j], dq);
     if (j == Lk - 1) { dS_own = dSj; Pk_own = Pkj; }
-    if (c == j && j < Lk) { dS_row[j] = dSj; Pk_row[j] = Pkj; }
+    if (w.c == j && j < Lk) { dS_row[j] = dSj; Pk_row[j] = Pkj; }
   }
-  ATTN_ST(p, p.dQ + b * s.q_bs + col, dq);
-  float4 dk = make_float4(dS_own * q.x, dS_own * q.y, dS_own * q.z, dS_own * q.w);
-  float4 dv = make_float4(Pk_own * dO.x, Pk_own * dO.y, Pk_own * dO.z, Pk_own * dO.w);
+  ATTN_ST(p.img, w.rows(p.dQ, s.q_bs), dq);
+  float4 dk = mul4(dS_own, q);
+  float4 dv = mul4(Pk_own, dO);
   for (int i0 = sp.step + 1; i0 < sp.T; i0 += 4) {          // later steps, four at a time: 8 row loads in flight
     float4 qn[4], gn[4];
     float a[4], bb[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int ic = min(i0 + u, sp.T - 1);
-      qn[u] = attn_ld4(p, sp.Q_all + ic * sp.q_ts + b * s.q_bs + col);
-      gn[u] = *reinterpret_cast<const float4*>(sp.dO_all + ic * sp.o_ts + b * s.o_bs + col);
-      const long long ci = ((long long)ic * nbh + bh) * sp.T + sp.step;
+      qn[u] = attn_ld4(p.img, w.rows(sp.Q_all + ic * sp.q_ts, s.q_bs));
+      gn[u] = *reinterpret_cast<const float4*>(w.rows(sp.dO_all + ic * sp.o_ts, s.o_bs));
+      const long long ci = ((long long)ic * nbh + w.bh) * sp.T + sp.step;
       a[u] = sp.dS_all[ci]; bb[u] = sp.Pk_all[ci];
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const float au = i0 + u < sp.T ? a[u] : 0.f, bu = i0 + u < sp.T ? bb[u] : 0.f;
-      dk.x = fmaf(au, qn[u].x, dk.x); dk.y = fmaf(au, qn[u].y, dk.y); dk.z = fmaf(au, qn[u].z, dk.z); dk.w = fmaf(au, qn[u].w, dk.w);
-      dv.x = fmaf(bu, gn[u].x, dv.x); dv.y = fmaf(bu, gn[u].y, dv.y); dv.z = fmaf(bu, gn[u].z, dv.z); dv.w = fmaf(bu, gn[u].w, dv.w);
+      dk = fma4(au, qn[u], dk);
+      dv = fma4(bu, gn[u], dv);
     }
   }
-  ATTN_ST(p, p.dK + b * s.k_bs + sp.step * s.k_rs + col, dk);
-  ATTN_ST(p, p.dV + b * s.v_bs + sp.step * s.v_rs + col, dv);
+  ATTN_ST(p.img, p.dK + w.b * s.k_bs + sp.step * s.k_rs + w.col, dk);
+  ATTN_ST(p.img, p.dV + w.b * s.v_bs + sp.step * s.v_rs + w.col, dv);
 }
 
 // Deferred K/V gradients of a Lq == 1 attention evaluated at TT query steps against the SAME K/V rows (decoder
@@ -505,68 +514,56 @@ __global__ __launch_bounds__(64 * WAVES) void attn_kvgrad_q1x4_kernel(const floa
                                                                       const float* __restrict__ dS_all, const float* __restrict__ Pk_all,
                                                                       float* __restrict__ dK, float* __restrict__ dV, AttnShape s, int T,
                                                                       int accum, const float* img_f, unsigned short* img_s) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int hg = s.H >> 2;
-  const long long g = (long long)blockIdx.x * WAVES + wave;
-  if (g >= (long long)s.nb * hg) return;
-  const int b = (int)(g / hg), h = (int)(g % hg) * 4 + (lane >> 4), c = lane & 15;
-  const long long bh = (long long)b * s.H + h;
-  const int Lk = s.Lk;
-  const int col = h * 64 + c * 4;
+  WAVE4_OR_RETURN(w, s);
+  const int Lk = w.Lk;
   const long long coef_ts = (long long)s.nb * s.H * Lk;
+  const AttnImage img = {img_f, img_s, 0, 0};      // bf16-storage mode: the K/V gradient rows are operands of the memory projection's dW and dX products
   float4 q[TT], go[TT];
   float aS[TT], aP[TT];
 #pragma unroll
   for (int i = 0; i < TT; ++i) {
     const int ic = min(i, T - 1);
-    q[i] = *reinterpret_cast<const float4*>(Q_all + ic * q_ts + b * s.q_bs + col);
-    go[i] = *reinterpret_cast<const float4*>(dO_all + ic * o_ts + b * s.o_bs + col);
-    const long long ci = ic * coef_ts + bh * Lk + min(c, Lk - 1);
+    q[i] = *reinterpret_cast<const float4*>(w.rows(Q_all + ic * q_ts, s.q_bs));
+    go[i] = *reinterpret_cast<const float4*>(w.rows(dO_all + ic * o_ts, s.o_bs));
+    const long long ci = ic * coef_ts + w.bh * Lk + min(w.c, Lk - 1);
     aS[i] = i < T ? dS_all[ci] : 0.f;      // lane c of a head group holds coefficient j = c
     aP[i] = i < T ? Pk_all[ci] : 0.f;
   }
-  float* dKb = dK + b * s.k_bs + col;
-  float* dVb = dV + b * s.v_bs + col;
+  float* dKb = w.rows(dK, s.k_bs);
+  float* dVb = w.rows(dV, s.v_bs);
   for (int j = 0; j < Lk; ++j) {
     float4 dk = make_float4(0.f, 0.f, 0.f, 0.f), dv = dk;
     if (accum) {
       dk = *reinterpret_cast<const float4*>(dKb + j * s.k_rs);
       dv = *reinterpret_cast<const float4*>(dVb + j * s.v_rs);
     }
-    const int src = (lane & 48) + j;
+    const int src = (threadIdx.x & 48) + j;      // = w.gbase + j, formed here: hipcc keeps w.gbase out of the loop's preheader at TT = 1
 #pragma unroll
     for (int i = 0; i < TT; ++i) {
       const float a = __shfl(aS[i], src, 64), bb = __shfl(aP[i], src, 64);
-      dk.x = fmaf(a, q[i].x, dk.x); dk.y = fmaf(a, q[i].y, dk.y); dk.z = fmaf(a, q[i].z, dk.z); dk.w = fmaf(a, q[i].w, dk.w);
-      dv.x = fmaf(bb, go[i].x, dv.x); dv.y = fmaf(bb, go[i].y, dv.y); dv.z = fmaf(bb, go[i].z, dv.z); dv.w = fmaf(bb, go[i].w, dv.w);
+      dk = fma4(a, q[i], dk);
+      dv = fma4(bb, go[i], dv);
     }
     *reinterpret_cast<float4*>(dKb + j * s.k_rs) = dk;
     *reinterpret_cast<float4*>(dVb + j * s.v_rs) = dv;
-    if (img_s) {      // bf16-storage mode: the K/V gradient rows are operands of the memory projection's dW and dX products
-      mansy_st_bf16x4(img_s + (dKb + j * s.k_rs - img_f), dk.x, dk.y, dk.z, dk.w);
-      mansy_st_bf16x4(img_s + (dVb + j * s.v_rs - img_f), dv.x, dv.y, dv.z, dv.w);
-    }
+    ATTN_IMG(img, dKb + j * s.k_rs, dk);
+    ATTN_IMG(img, dVb + j * s.v_rs, dv);
   }
 }
 
-// ---- Lq == Lk == S <= 10, dh == 64, H % 4 == 0 (encoder self-attention): four heads per wave, 16 lanes x float4 per head,
+// ---- Lq == Lk == S <= 10 on the 4-heads-per-wave layout (encoder self-attention):
 // every Q / K / V (/ dO) row of the (batch, 4-head) group loaded up front as full 1-KiB wave accesses.  Lane c of a head
 // group owns score column j = c (softmax output, dropout mask, dS); columns are broadcast inside the 16-lane group when
 // a sum over j needs them.  ST = compile-time S bound (rows >= S re-read row S-1 and are masked).
 template <int ST>
 __global__ __launch_bounds__(64 * WAVES) void attn_fwd_sx4_kernel(AttnPtrs p, AttnShape s, MansyDrop drop) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int hg = s.H >> 2;
-  const long long g = (long long)blockIdx.x * WAVES + wave;
-  if (g >= (long long)s.nb * hg) return;
-  const int b = (int)(g / hg), h = (int)(g % hg) * 4 + (lane >> 4), c = lane & 15, gbase = lane & 48;
-  const long long bh = (long long)b * s.H + h;
-  const int S = s.Lk;
-  const int col = h * 64 + c * 4;
-  const float* Qb = p.Q + b * s.q_bs + col;
-  const float* Kb = p.K + b * s.k_bs + col;
-  const float* Vb = p.V + b * s.v_bs + col;
-  float* Ob = p.O + b * s.o_bs + col;
+  WAVE4_OR_RETURN(w, s);
+  const int c = w.c, gbase = w.gbase;
+  const int S = w.Lk;
+  const float* Qb = w.rows(p.Q, s.q_bs);
+  const float* Kb = w.rows(p.K, s.k_bs);
+  const float* Vb = w.rows(p.V, s.v_bs);
+  float* Ob = w.rows(p.O, s.o_bs);
   float4 q[ST], k[ST], v[ST];
 #pragma unroll
   for (int j = 0; j < ST; ++j) {
@@ -575,7 +572,7 @@ __global__ __launch_bounds__(64 * WAVES) void attn_fwd_sx4_kernel(AttnPtrs p, At
     k[j] = *reinterpret_cast<const float4*>(Kb + jc * s.k_rs);
     v[j] = *reinterpret_cast<const float4*>(Vb + jc * s.v_rs);
   }
-  const float ds = drop.p > 0.f ? 1.f / (1.f - drop.p) : 1.f;
+  const float ds = drop_scale(drop);
 #pragma unroll
   for (int i = 0; i < ST; ++i) {
     if (i < S) {
@@ -593,34 +590,26 @@ __global__ __launch_bounds__(64 * WAVES) void attn_fwd_sx4_kernel(AttnPtrs p, At
       float pc = 0.f;                               // this lane's column
 #pragma unroll
       for (int j = 0; j < ST; ++j) if (c == j) pc = sc[j] * inv;
-      const long long prow = (bh * S + i) * S;
+      const long long prow = (w.bh * S + i) * S;
       if (c < S && p.P) p.P[prow + c] = pc;
-      if (drop.p > 0.f) pc = mansy_keep(drop.seed, drop.site, drop.base + (uint32_t)(prow + c), drop.p) ? pc * ds : 0.f;
+      if (drop.p > 0.f) pc = kept(drop, prow + c) ? pc * ds : 0.f;
       float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
-      for (int j = 0; j < ST; ++j) {
-        const float pv = __shfl(pc, gbase + j, 64);      // 0 for j >= S
-        o.x = fmaf(pv, v[j].x, o.x); o.y = fmaf(pv, v[j].y, o.y); o.z = fmaf(pv, v[j].z, o.z); o.w = fmaf(pv, v[j].w, o.w);
-      }
-      ATTN_ST(p, Ob + i * s.o_rs, o);
+      for (int j = 0; j < ST; ++j) o = fma4(__shfl(pc, gbase + j, 64), v[j], o);      // (the shuffled probability is 0 for j >= S)
+      ATTN_ST(p.img, Ob + i * s.o_rs, o);
     }
   }
 }
 
 template <int ST>
 __global__ __launch_bounds__(64 * WAVES) void attn_bwd_sx4_kernel(AttnPtrs p, AttnShape s, MansyDrop drop, int accum_kv) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int hg = s.H >> 2;
-  const long long g = (long long)blockIdx.x * WAVES + wave;
-  if (g >= (long long)s.nb * hg) return;
-  const int b = (int)(g / hg), h = (int)(g % hg) * 4 + (lane >> 4), c = lane & 15, gbase = lane & 48;
-  const long long bh = (long long)b * s.H + h;
-  const int S = s.Lk;
-  const int col = h * 64 + c * 4;
-  const float* Qb = p.Q + b * s.q_bs + col;
-  const float* Kb = p.K + b * s.k_bs + col;
-  const float* Vb = p.V + b * s.v_bs + col;
-  const float* Gb = p.dO + b * s.o_bs + col;
+  WAVE4_OR_RETURN(w, s);
+  const int c = w.c, gbase = w.gbase;
+  const int S = w.Lk;
+  const float* Qb = w.rows(p.Q, s.q_bs);
+  const float* Kb = w.rows(p.K, s.k_bs);
+  const float* Vb = w.rows(p.V, s.v_bs);
+  const float* Gb = w.rows(p.dO, s.o_bs);
   float4 k[ST], v[ST], go[ST];
   float pc[ST];                                     // P[i][c]: this lane's column of every row
   const int cc = min(c, S - 1);
@@ -630,11 +619,11 @@ __global__ __launch_bounds__(64 * WAVES) void attn_bwd_sx4_kernel(AttnPtrs p, At
     k[j] = *reinterpret_cast<const float4*>(Kb + jc * s.k_rs);
     v[j] = *reinterpret_cast<const float4*>(Vb + jc * s.v_rs);
     go[j] = *reinterpret_cast<const float4*>(Gb + jc * s.o_rs);
-    pc[j] = p.P[(bh * S + jc) * S + cc];
+    pc[j] = p.P[(w.bh * S + jc) * S + cc];
   }
-  const float ds = drop.p > 0.f ? 1.f / (1.f - drop.p) : 1.f;
+  const float ds = drop_scale(drop);
   float dSc[ST], Pdc[ST];                           // dS[i][c], dropped P[i][c]
-  float* dQb = p.dQ + b * s.q_bs + col;
+  float* dQb = w.rows(p.dQ, s.q_bs);
 #pragma unroll
   for (int i = 0; i < ST; ++i) {
     dSc[i] = 0.f; Pdc[i] = 0.f;
@@ -646,7 +635,7 @@ __global__ __launch_bounds__(64 * WAVES) void attn_bwd_sx4_kernel(AttnPtrs p, At
         if (c == j) dpc = t;
       }
       float kc = 1.f;
-      if (drop.p > 0.f) kc = mansy_keep(drop.seed, drop.site, drop.base + (uint32_t)((bh * S + i) * S + c), drop.p) ? ds : 0.f;
+      if (drop.p > 0.f) kc = kept(drop, (w.bh * S + i) * S + c) ? ds : 0.f;
       const float Pc = c < S ? pc[i] : 0.f;
       const float dPk = dpc * kc;
       const float delta = group16_sum(Pc * dPk);
@@ -654,11 +643,8 @@ __global__ __launch_bounds__(64 * WAVES) void attn_bwd_sx4_kernel(AttnPtrs p, At
       Pdc[i] = Pc * kc;
       float4 dq = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
-      for (int j = 0; j < ST; ++j) {
-        const float a = __shfl(dSc[i], gbase + j, 64);
-        dq.x = fmaf(a, k[j].x, dq.x); dq.y = fmaf(a, k[j].y, dq.y); dq.z = fmaf(a, k[j].z, dq.z); dq.w = fmaf(a, k[j].w, dq.w);
-      }
-      ATTN_ST(p, dQb + i * s.q_rs, dq);
+      for (int j = 0; j < ST; ++j) dq = fma4(__shfl(dSc[i], gbase + j, 64), k[j], dq);
+      ATTN_ST(p.img, dQb + i * s.q_rs, dq);
     }
   }
   // K / V rows are dead from here; the Q rows take their registers (fetched only now: all five row sets at once would
@@ -667,8 +653,8 @@ __global__ __launch_bounds__(64 * WAVES) void attn_bwd_sx4_kernel(AttnPtrs p, At
   float4 q[ST];
 #pragma unroll
   for (int j = 0; j < ST; ++j) q[j] = *reinterpret_cast<const float4*>(Qb + min(j, S - 1) * s.q_rs);
-  float* dKb = p.dK + b * s.k_bs + col;
-  float* dVb = p.dV + b * s.v_bs + col;
+  float* dKb = w.rows(p.dK, s.k_bs);
+  float* dVb = w.rows(p.dV, s.v_bs);
 #pragma unroll
   for (int j = 0; j < ST; ++j) {
     if (j < S) {
@@ -680,56 +666,50 @@ __global__ __launch_bounds__(64 * WAVES) void attn_bwd_sx4_kernel(AttnPtrs p, At
 #pragma unroll
       for (int i = 0; i < ST; ++i) {               // rows i >= S carry zeros
         const float a = __shfl(dSc[i], gbase + j, 64), bb = __shfl(Pdc[i], gbase + j, 64);
-        dk.x = fmaf(a, q[i].x, dk.x); dk.y = fmaf(a, q[i].y, dk.y); dk.z = fmaf(a, q[i].z, dk.z); dk.w = fmaf(a, q[i].w, dk.w);
-        dv.x = fmaf(bb, go[i].x, dv.x); dv.y = fmaf(bb, go[i].y, dv.y); dv.z = fmaf(bb, go[i].z, dv.z); dv.w = fmaf(bb, go[i].w, dv.w);
+        dk = fma4(a, q[i], dk);
+        dv = fma4(bb, go[i], dv);
       }
-      ATTN_ST(p, dKb + j * s.k_rs, dk);
-      ATTN_ST(p, dVb + j * s.v_rs, dv);
+      ATTN_ST(p.img, dKb + j * s.k_rs, dk);
+      ATTN_ST(p.img, dVb + j * s.v_rs, dv);
     }
   }
 }
 
+// ---- launch side.  Compile-time row bounds: a list below is exactly the set of instantiations of the kernels dispatched over it.
+// q1x4 / kvgrad: exact for the decode lengths the engine produces (1..10), then 12 and 16
+#define MANSY_Q1X4_BOUNDS 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 12, 16
 constexpr int SX4_MAX = 10;     // 4 x S float4 row sets + coefficients fit the register file up to here
-#define MANSY_SX4_DISPATCH(KERNEL, S_, ...)                                                                \
-  switch (S_) {                                                                                            \
-    case 2: MANSY_LAUNCH(KERNEL<2>, __VA_ARGS__); break;                                             \
-    case 3: MANSY_LAUNCH(KERNEL<3>, __VA_ARGS__); break;                                             \
-    case 4: MANSY_LAUNCH(KERNEL<4>, __VA_ARGS__); break;                                             \
-    case 5: MANSY_LAUNCH(KERNEL<5>, __VA_ARGS__); break;                                             \
-    case 6: MANSY_LAUNCH(KERNEL<6>, __VA_ARGS__); break;                                             \
-    case 7: MANSY_LAUNCH(KERNEL<7>, __VA_ARGS__); break;                                             \
-    case 8: MANSY_LAUNCH(KERNEL<8>, __VA_ARGS__); break;                                             \
-    case 9: MANSY_LAUNCH(KERNEL<9>, __VA_ARGS__); break;                                             \
-    default: MANSY_LAUNCH(KERNEL<10>, __VA_ARGS__); break;                                           \
-  }
-static bool sx4_ok(const AttnShape& s, const void* a, const void* b, const void* c, const void* d) {
-  auto al = [](const void* x) { return (reinterpret_cast<uintptr_t>(x) & 15) == 0; };
-  return s.Lq == s.Lk && s.Lk >= 2 && s.Lk <= SX4_MAX && s.dh == 64 && (s.H % 4) == 0 && (s.q_bs % 4) == 0 && (s.q_rs % 4) == 0 &&
-         (s.k_bs % 4) == 0 && (s.k_rs % 4) == 0 && (s.v_bs % 4) == 0 && (s.v_rs % 4) == 0 && (s.o_bs % 4) == 0 && (s.o_rs % 4) == 0 &&
-         al(a) && al(b) && al(c) && al(d);
+#define MANSY_SX4_BOUNDS 2, 3, 4, 5, 6, 7, 8, 9, 10
+// f(std::integral_constant<int, B>) for the first bound B >= n of the ascending list (the last one when there is none)
+template <int B, int... Rest, class F>
+void with_bound(int n, const F& f) {
+  if constexpr (sizeof...(Rest) == 0) f(std::integral_constant<int, B>{});
+  else if (n <= B) f(std::integral_constant<int, B>{});
+  else with_bound<Rest...>(n, f);
 }
+#define MANSY_BOUND(B) decltype(B)::value
 
-// LKT buckets: exact for the decode lengths the engine produces (1..10), then 12 and 16
-#define MANSY_Q1X4_DISPATCH(KERNEL, Lk, ...)                                                               \
-  switch (Lk) {                                                                                            \
-    case 1: MANSY_LAUNCH(KERNEL<1>, __VA_ARGS__); break;                                             \
-    case 2: MANSY_LAUNCH(KERNEL<2>, __VA_ARGS__); break;                                             \
-    case 3: MANSY_LAUNCH(KERNEL<3>, __VA_ARGS__); break;                                             \
-    case 4: MANSY_LAUNCH(KERNEL<4>, __VA_ARGS__); break;                                             \
-    case 5: MANSY_LAUNCH(KERNEL<5>, __VA_ARGS__); break;                                             \
-    case 6: MANSY_LAUNCH(KERNEL<6>, __VA_ARGS__); break;                                             \
-    case 7: MANSY_LAUNCH(KERNEL<7>, __VA_ARGS__); break;                                             \
-    case 8: MANSY_LAUNCH(KERNEL<8>, __VA_ARGS__); break;                                             \
-    case 9: MANSY_LAUNCH(KERNEL<9>, __VA_ARGS__); break;                                             \
-    case 10: MANSY_LAUNCH(KERNEL<10>, __VA_ARGS__); break;                                           \
-    case 11: case 12: MANSY_LAUNCH(KERNEL<12>, __VA_ARGS__); break;                                  \
-    default: MANSY_LAUNCH(KERNEL<16>, __VA_ARGS__); break;                                           \
-  }
+struct LaunchCfg { dim3 grid, block; };      // WAVES waves per workgroup
+LaunchCfg launch_cfg(long long n_waves) { return {dim3(mansy_ceil_div(n_waves, WAVES)), dim3(64 * WAVES)}; }
 
-static bool q1x4_ok(const AttnShape& s, const void* a, const void* b, const void* c, const void* d) {
-  auto al = [](const void* x) { return (reinterpret_cast<uintptr_t>(x) & 15) == 0; };
-  return s.Lq == 1 && s.dh == 64 && (s.H % 4) == 0 && (s.q_bs % 4) == 0 && (s.k_bs % 4) == 0 && (s.k_rs % 4) == 0 && (s.v_bs % 4) == 0 &&
-         (s.v_rs % 4) == 0 && (s.o_bs % 4) == 0 && al(a) && al(b) && al(c) && al(d);
+template <class... Ptrs>
+bool aligned16(Ptrs... ptrs) { return (((reinterpret_cast<uintptr_t>(static_cast<const void*>(ptrs)) & 15) == 0) && ...); }
+// the 4-heads-per-wave layout: float4 pieces of rows that stay 16-byte aligned from batch entry to batch entry and K / V row to row
+// (qo_rows: also from Q / O row to row -- the S x S kernels)
+bool vec4_layout_ok(const AttnShape& s, bool qo_rows) {
+  return s.dh == 64 && (s.H % 4) == 0 && (s.q_bs % 4) == 0 && (s.k_bs % 4) == 0 && (s.k_rs % 4) == 0 && (s.v_bs % 4) == 0 && (s.v_rs % 4) == 0 &&
+         (s.o_bs % 4) == 0 && (!qo_rows || ((s.q_rs % 4) == 0 && (s.o_rs % 4) == 0));
+}
+bool sx4_ok(const AttnShape& s, const void* a, const void* b, const void* c, const void* d) {
+  return s.Lq == s.Lk && s.Lk >= 2 && s.Lk <= SX4_MAX && vec4_layout_ok(s, true) && aligned16(a, b, c, d);
+}
+bool q1x4_ok(const AttnShape& s, const void* a, const void* b, const void* c, const void* d) {
+  return s.Lq == 1 && vec4_layout_ok(s, false) && aligned16(a, b, c, d);
+}
+// `only` and `kv16` mean something with an image only
+AttnImage checked(AttnImage img) {
+  if (!img.s) { img.only = 0; img.kv16 = 0; }
+  return img;
 }
 
 int check_shape(const AttnShape& s) {
@@ -742,73 +722,78 @@ int check_shape(const AttnShape& s) {
 }  // namespace
 
 int mansy_launch_attn_fwd(const float* Q, const float* K, const float* V, float* O, float* P_save, const AttnShape& s,
-                          MansyDrop drop, hipStream_t st, const float* img_f, unsigned short* img_s, int img_only, int kv16) {
+                          MansyDrop drop, hipStream_t st, AttnImage img) {
   int rc = check_shape(s); if (rc) return rc;
   MANSY_REQUIRE(Q && K && V && O, "attn_fwd: null pointer");
-  MANSY_REQUIRE(!kv16 || q1x4_ok(s, Q, K, V, O), "attn_fwd: the bf16 K/V cache is read by the 4-heads-per-wave Lq = 1 kernel only");
+  MANSY_REQUIRE(!img.kv16 || q1x4_ok(s, Q, K, V, O), "attn_fwd: the bf16 K/V cache is read by the 4-heads-per-wave Lq = 1 kernel only");
   const long long n = (long long)s.nb * s.H;
   if (n == 0) return MANSY_OK;
-  AttnPtrs p = {Q, K, V, O, P_save, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, img_f, img_s, img_s ? img_only : 0, img_s ? kv16 : 0};
-  MANSY_REQUIRE(!img_s || q1x4_ok(s, Q, K, V, O) || sx4_ok(s, Q, K, V, O), "attn_fwd: the bf16 image needs the 4-heads-per-wave kernels");
+  AttnPtrs p = {Q, K, V, O, P_save, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, checked(img)};
+  MANSY_REQUIRE(!img.s || q1x4_ok(s, Q, K, V, O) || sx4_ok(s, Q, K, V, O), "attn_fwd: the bf16 image needs the 4-heads-per-wave kernels");
+  const LaunchCfg c4 = launch_cfg(n / 4), c1 = launch_cfg(n);
   if (q1x4_ok(s, Q, K, V, O))
-    MANSY_Q1X4_DISPATCH(attn_fwd_q1x4_kernel, s.Lk, dim3(mansy_ceil_div(n / 4, WAVES)), dim3(64 * WAVES), 0, st, p, s, drop)
+    with_bound<MANSY_Q1X4_BOUNDS>(s.Lk, [&](auto B) { MANSY_LAUNCH(attn_fwd_q1x4_kernel<MANSY_BOUND(B)>, c4.grid, c4.block, 0, st, p, s, drop); });
   else if (sx4_ok(s, Q, K, V, O))
-    MANSY_SX4_DISPATCH(attn_fwd_sx4_kernel, s.Lk, dim3(mansy_ceil_div(n / 4, WAVES)), dim3(64 * WAVES), 0, st, p, s, drop)
-  else if (s.Lq == 1) MANSY_LAUNCH(attn_fwd_q1_kernel, dim3(mansy_ceil_div(n, WAVES)), dim3(64 * WAVES), 0, st, p, s, drop);
-  else MANSY_LAUNCH(attn_fwd_kernel, dim3(mansy_ceil_div(n, WAVES)), dim3(64 * WAVES), 0, st, p, s, drop);
+    with_bound<MANSY_SX4_BOUNDS>(s.Lk, [&](auto B) { MANSY_LAUNCH(attn_fwd_sx4_kernel<MANSY_BOUND(B)>, c4.grid, c4.block, 0, st, p, s, drop); });
+  else if (s.Lq == 1) MANSY_LAUNCH(attn_fwd_q1_kernel, c1.grid, c1.block, 0, st, p, s, drop);
+  else MANSY_LAUNCH(attn_fwd_kernel, c1.grid, c1.block, 0, st, p, s, drop);
   MANSY_LAUNCH_CHECK();
   return MANSY_OK;
 }
 
 int mansy_launch_attn_bwd(const float* Q, const float* K, const float* V, const float* P_save, const float* dO, float* dQ,
-                          float* dK, float* dV, const AttnShape& s, MansyDrop drop, int accum_kv, hipStream_t st, const float* img_f, unsigned short* img_s, int img_only) {
+                          float* dK, float* dV, const AttnShape& s, MansyDrop drop, int accum_kv, hipStream_t st, AttnImage img) {
   int rc = check_shape(s); if (rc) return rc;
   MANSY_REQUIRE(Q && K && V && P_save && dO && dQ && dK && dV, "attn_bwd: null pointer");
   const long long n = (long long)s.nb * s.H;
   if (n == 0) return MANSY_OK;
-  AttnPtrs p = {Q, K, V, nullptr, const_cast<float*>(P_save), dO, dQ, dK, dV, nullptr, nullptr, img_f, img_s, (img_s && !accum_kv) ? img_only : 0, 0};
-  MANSY_REQUIRE(!img_s || (sx4_ok(s, Q, K, V, dO) && sx4_ok(s, dQ, dK, dV, dO) && !q1x4_ok(s, Q, K, V, dO)), "attn_bwd: the bf16 image is kept by the encoder (S x S) kernel only");
+  img = checked(img);
+  if (accum_kv) img.only = 0;      // accumulated K / V gradient rows are read back as floats
+  img.kv16 = 0;
+  AttnPtrs p = {Q, K, V, nullptr, const_cast<float*>(P_save), dO, dQ, dK, dV, nullptr, nullptr, img};
+  MANSY_REQUIRE(!img.s || (sx4_ok(s, Q, K, V, dO) && sx4_ok(s, dQ, dK, dV, dO) && !q1x4_ok(s, Q, K, V, dO)), "attn_bwd: the bf16 image is kept by the encoder (S x S) kernel only");
+  const LaunchCfg c4 = launch_cfg(n / 4), c1 = launch_cfg(n);
   if (q1x4_ok(s, Q, K, V, dO) && q1x4_ok(s, dQ, dK, dV, dO))
-    MANSY_Q1X4_DISPATCH(attn_bwd_q1x4_kernel, s.Lk, dim3(mansy_ceil_div(n / 4, WAVES)), dim3(64 * WAVES), 0, st, p, s, drop, accum_kv)
+    with_bound<MANSY_Q1X4_BOUNDS>(s.Lk, [&](auto B) { MANSY_LAUNCH(attn_bwd_q1x4_kernel<MANSY_BOUND(B)>, c4.grid, c4.block, 0, st, p, s, drop, accum_kv); });
   else if (sx4_ok(s, Q, K, V, dO) && sx4_ok(s, dQ, dK, dV, dO))
-    MANSY_SX4_DISPATCH(attn_bwd_sx4_kernel, s.Lk, dim3(mansy_ceil_div(n / 4, WAVES)), dim3(64 * WAVES), 0, st, p, s, drop, accum_kv)
-  else if (s.Lq == 1) MANSY_LAUNCH(attn_bwd_q1_kernel, dim3(mansy_ceil_div(n, WAVES)), dim3(64 * WAVES), 0, st, p, s, drop, accum_kv);
-  else MANSY_LAUNCH(attn_bwd_kernel, dim3(mansy_ceil_div(n, WAVES)), dim3(64 * WAVES), 0, st, p, s, drop, accum_kv);
+    with_bound<MANSY_SX4_BOUNDS>(s.Lk, [&](auto B) { MANSY_LAUNCH(attn_bwd_sx4_kernel<MANSY_BOUND(B)>, c4.grid, c4.block, 0, st, p, s, drop, accum_kv); });
+  else if (s.Lq == 1) MANSY_LAUNCH(attn_bwd_q1_kernel, c1.grid, c1.block, 0, st, p, s, drop, accum_kv);
+  else MANSY_LAUNCH(attn_bwd_kernel, c1.grid, c1.block, 0, st, p, s, drop, accum_kv);
   MANSY_LAUNCH_CHECK();
   return MANSY_OK;
 }
 
-// ---- deferred K/V gradients (decoder cross-attention).  Shape-only test; pointers must be 16-byte aligned.
+// ---- deferred K/V gradients (decoder cross-attention) and the pull form of the decoder self-attention backward: one condition.
+// Shape-only test; pointers must be 16-byte aligned.
 int mansy_attn_deferred_kv_ok(const AttnShape& s, int T) {
-  return s.Lq == 1 && s.dh == 64 && (s.H % 4) == 0 && s.Lk >= 1 && s.Lk <= LMAX && T >= 1 && T <= LMAX && (s.q_bs % 4) == 0 &&
-         (s.k_bs % 4) == 0 && (s.k_rs % 4) == 0 && (s.v_bs % 4) == 0 && (s.v_rs % 4) == 0 && (s.o_bs % 4) == 0;
+  return s.Lq == 1 && vec4_layout_ok(s, false) && s.Lk >= 1 && s.Lk <= LMAX && T >= 1 && T <= LMAX;
 }
 // One step: dQ only; dS_out / Pk_out [nb*H, Lk] receive the coefficients mansy_launch_attn_kvgrad sums over the steps.
 int mansy_launch_attn_bwd_dq(const float* Q, const float* K, const float* V, const float* P_save, const float* dO, float* dQ,
-                             float* dS_out, float* Pk_out, const AttnShape& s, MansyDrop drop, hipStream_t st, const float* img_f, unsigned short* img_s, int img_only, int kv16) {
+                             float* dS_out, float* Pk_out, const AttnShape& s, MansyDrop drop, hipStream_t st, AttnImage img) {
   int rc = check_shape(s); if (rc) return rc;
   MANSY_REQUIRE(Q && K && V && P_save && dO && dQ && dS_out && Pk_out, "attn_bwd_dq: null pointer");
   MANSY_REQUIRE(q1x4_ok(s, Q, K, V, dO) && q1x4_ok(s, dQ, K, V, dO), "attn_bwd_dq: shape / alignment not on the 4-heads-per-wave path");
   const long long n = (long long)s.nb * s.H;
   if (n == 0) return MANSY_OK;
-  AttnPtrs p = {Q, K, V, nullptr, const_cast<float*>(P_save), dO, dQ, nullptr, nullptr, dS_out, Pk_out, img_f, img_s, img_s ? img_only : 0, img_s ? kv16 : 0};
-  MANSY_Q1X4_DISPATCH(attn_bwd_q1x4_kernel, s.Lk, dim3(mansy_ceil_div(n / 4, WAVES)), dim3(64 * WAVES), 0, st, p, s, drop, 0)
+  AttnPtrs p = {Q, K, V, nullptr, const_cast<float*>(P_save), dO, dQ, nullptr, nullptr, dS_out, Pk_out, checked(img)};
+  const LaunchCfg c4 = launch_cfg(n / 4);
+  with_bound<MANSY_Q1X4_BOUNDS>(s.Lk, [&](auto B) { MANSY_LAUNCH(attn_bwd_q1x4_kernel<MANSY_BOUND(B)>, c4.grid, c4.block, 0, st, p, s, drop, 0); });
   MANSY_LAUNCH_CHECK();
   return MANSY_OK;
 }
 // Q_all / dO_all: step i at + i*q_ts / + i*o_ts (batch strides from s); dS_all / Pk_all: [T][nb*H][Lk].
 int mansy_launch_attn_kvgrad(const float* Q_all, long long q_ts, const float* dO_all, long long o_ts, const float* dS_all,
-                             const float* Pk_all, float* dK, float* dV, const AttnShape& s, int T, int accum, hipStream_t st, const float* img_f,
-                             unsigned short* img_s) {
+                             const float* Pk_all, float* dK, float* dV, const AttnShape& s, int T, int accum, hipStream_t st, AttnImage img) {
   MANSY_REQUIRE(Q_all && dO_all && dS_all && Pk_all && dK && dV, "attn_kvgrad: null pointer");
   MANSY_REQUIRE(mansy_attn_deferred_kv_ok(s, T) && (q_ts % 4) == 0 && (o_ts % 4) == 0, "attn_kvgrad: unsupported shape");
-  auto al = [](const void* x) { return (reinterpret_cast<uintptr_t>(x) & 15) == 0; };
-  MANSY_REQUIRE(al(Q_all) && al(dO_all) && al(dK) && al(dV), "attn_kvgrad: pointers must be 16-byte aligned");
+  MANSY_REQUIRE(aligned16(Q_all, dO_all, dK, dV), "attn_kvgrad: pointers must be 16-byte aligned");
   const long long n = (long long)s.nb * s.H;
   if (n == 0) return MANSY_OK;
-#define MANSY_KVGRAD_ARGS dim3(mansy_ceil_div(n / 4, WAVES)), dim3(64 * WAVES), 0, st, Q_all, q_ts, dO_all, o_ts, dS_all, Pk_all, dK, dV, s, T, accum, img_f, img_s
-  MANSY_Q1X4_DISPATCH(attn_kvgrad_q1x4_kernel, T, MANSY_KVGRAD_ARGS)
-#undef MANSY_KVGRAD_ARGS
+  const LaunchCfg c4 = launch_cfg(n / 4);
+  with_bound<MANSY_Q1X4_BOUNDS>(T, [&](auto B) {
+    MANSY_LAUNCH(attn_kvgrad_q1x4_kernel<MANSY_BOUND(B)>, c4.grid, c4.block, 0, st, Q_all, q_ts, dO_all, o_ts, dS_all, Pk_all, dK, dV, s, T, accum, img.f, img.s);
+  });
   MANSY_LAUNCH_CHECK();
   return MANSY_OK;
 }
@@ -817,20 +802,20 @@ int mansy_launch_attn_kvgrad(const float* Q_all, long long q_ts, const float* dO
 // Q_all / dO_all: step i at + i*q_ts / + i*o_ts floats; dS_all / Pk_all: [T][nb*H][T] (rows > step already written by the
 // calls for the later steps; this call writes row `step`).  dQ: this step's [nb, H*64]; dK / dV: K/V gradient slabs, row `step`
 // is overwritten.
-int mansy_attn_selfpull_ok(const AttnShape& s, int T) { return mansy_attn_deferred_kv_ok(s, T); }
 int mansy_launch_attn_bwd_selfpull(const float* Q_all, long long q_ts, const float* K, const float* V, const float* P_save,
                                    const float* dO_all, long long o_ts, float* dQ, float* dK, float* dV, float* dS_all, float* Pk_all,
-                                   const AttnShape& s, int T, int step, MansyDrop drop, hipStream_t st, const float* img_f, unsigned short* img_s, int img_only, int kv16) {
+                                   const AttnShape& s, int T, int step, MansyDrop drop, hipStream_t st, AttnImage img) {
   int rc = check_shape(s); if (rc) return rc;
   MANSY_REQUIRE(Q_all && K && V && P_save && dO_all && dQ && dK && dV && dS_all && Pk_all, "attn_bwd_selfpull: null pointer");
-  MANSY_REQUIRE(step >= 0 && step < T && s.Lk == step + 1 && mansy_attn_selfpull_ok(s, T) && (q_ts % 4) == 0 && (o_ts % 4) == 0,
+  MANSY_REQUIRE(step >= 0 && step < T && s.Lk == step + 1 && mansy_attn_deferred_kv_ok(s, T) && (q_ts % 4) == 0 && (o_ts % 4) == 0,
                 "attn_bwd_selfpull: unsupported shape (Lk=%d step=%d T=%d)", s.Lk, step, T);
   MANSY_REQUIRE(q1x4_ok(s, Q_all, K, V, dO_all) && q1x4_ok(s, dQ, dK, dV, dO_all), "attn_bwd_selfpull: alignment");
   const long long n = (long long)s.nb * s.H;
   if (n == 0) return MANSY_OK;
-  AttnPtrs p = {nullptr, K, V, nullptr, const_cast<float*>(P_save), nullptr, dQ, dK, dV, nullptr, nullptr, img_f, img_s, img_s ? img_only : 0, img_s ? kv16 : 0};
+  AttnPtrs p = {nullptr, K, V, nullptr, const_cast<float*>(P_save), nullptr, dQ, dK, dV, nullptr, nullptr, checked(img)};
   SelfPull sp = {Q_all, q_ts, dO_all, o_ts, dS_all, Pk_all, T, step};
-  MANSY_Q1X4_DISPATCH(attn_bwd_selfpull_q1x4_kernel, s.Lk, dim3(mansy_ceil_div(n / 4, WAVES)), dim3(64 * WAVES), 0, st, p, s, drop, sp)
+  const LaunchCfg c4 = launch_cfg(n / 4);
+  with_bound<MANSY_Q1X4_BOUNDS>(s.Lk, [&](auto B) { MANSY_LAUNCH(attn_bwd_selfpull_q1x4_kernel<MANSY_BOUND(B)>, c4.grid, c4.block, 0, st, p, s, drop, sp); });
   MANSY_LAUNCH_CHECK();
   return MANSY_OK;
 }

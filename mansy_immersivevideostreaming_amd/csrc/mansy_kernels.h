@@ -112,37 +112,40 @@ struct AttnShape {
   long long q_bs, q_rs, k_bs, k_rs, v_bs, v_rs, o_bs, o_rs;
   float scale;
 };
+// bf16 images of attention rows (bf16-storage mode; 4-heads-per-wave kernels only).  The float4 an attention kernel stores at address a also goes,
+// rounded, to s + (a - f): one mapping for O / dQ / dK / dV (rows of one slab).  The default is no image.
+struct AttnImage {
+  const float* f = nullptr; unsigned short* s = nullptr;
+  int only = 0;      // != 0 (with s): the rows are operands of dense products and nothing else -- the float4 store is skipped
+  int kv16 = 0;      // != 0 (with s; Lq = 1 kernels): the K / V rows (and the pull form's Q rows) are READ from their bf16 images -- the K/V cache of the
+                     // bf16-storage mode is bf16 in HBM (written by the projection's epilogue): half the cache traffic
+};
 // P_save: [nb*H, Lq, Lk] softmax probabilities BEFORE dropout (needed by backward); may be null in eval.
-// img_f / img_s (all attention launchers; bf16-storage mode): the output rows' bf16 image -- the float4 stored at address a also goes to img_s + (a - img_f)
 int mansy_launch_attn_fwd(const float* Q, const float* K, const float* V, float* O, float* P_save,
-                          const AttnShape& s, MansyDrop drop, hipStream_t st, const float* img_f = nullptr, unsigned short* img_s = nullptr, int img_only = 0,
-                          int kv16 = 0);      // kv16 (Lq = 1 kernels): K / V rows are read from their bf16 images (bf16 K/V cache)
-// dQ is overwritten; dK/dV are accumulated (+=) when accum_kv != 0, else overwritten.
+                          const AttnShape& s, MansyDrop drop, hipStream_t st, AttnImage img = {});
+// dQ is overwritten; dK/dV are accumulated (+=) when accum_kv != 0, else overwritten (and then never image-only).
 // dq/dk/dv use the q/k/v strides of `s`; dO uses the o strides.
 int mansy_launch_attn_bwd(const float* Q, const float* K, const float* V, const float* P_save, const float* dO,
                           float* dQ, float* dK, float* dV, const AttnShape& s, MansyDrop drop, int accum_kv,
-                          hipStream_t st, const float* img_f = nullptr, unsigned short* img_s = nullptr, int img_only = 0);
+                          hipStream_t st, AttnImage img = {});
 
 // Deferred K/V gradients for a Lq == 1 attention evaluated at T steps against the same K/V rows (decoder cross-attention):
 // per step mansy_launch_attn_bwd_dq writes dQ and the step's coefficients (dS, dropped P: [nb*H, Lk] each); one
-// mansy_launch_attn_kvgrad then forms dK[j] = sum_i dS_i[j] q_i, dV[j] = sum_i Pk_i[j] dO_i (overwrites, or += when accum).
-// Q_all / dO_all hold step i at + i*q_ts / + i*o_ts; dS_all / Pk_all are [T][nb*H][Lk].
+// mansy_launch_attn_kvgrad then forms dK[j] = sum_i dS_i[j] q_i, dV[j] = sum_i Pk_i[j] dO_i (overwrites, or += when accum; the floats are always
+// stored).  Q_all / dO_all hold step i at + i*q_ts / + i*o_ts; dS_all / Pk_all are [T][nb*H][Lk].
+// mansy_attn_deferred_kv_ok: the shape condition of these launchers and of the pull form below (there with s.Lk = T).
 int mansy_attn_deferred_kv_ok(const AttnShape& s, int T);
 int mansy_launch_attn_bwd_dq(const float* Q, const float* K, const float* V, const float* P_save, const float* dO, float* dQ,
-                             float* dS_out, float* Pk_out, const AttnShape& s, MansyDrop drop, hipStream_t st,
-                             const float* img_f = nullptr, unsigned short* img_s = nullptr, int img_only = 0, int kv16 = 0);
+                             float* dS_out, float* Pk_out, const AttnShape& s, MansyDrop drop, hipStream_t st, AttnImage img = {});
 int mansy_launch_attn_kvgrad(const float* Q_all, long long q_ts, const float* dO_all, long long o_ts, const float* dS_all,
-                             const float* Pk_all, float* dK, float* dV, const AttnShape& s, int T, int accum, hipStream_t st,
-                             const float* img_f = nullptr, unsigned short* img_s = nullptr);      // + bf16 images of dK / dV at img_s + (p - img_f)
+                             const float* Pk_all, float* dK, float* dV, const AttnShape& s, int T, int accum, hipStream_t st, AttnImage img = {});
 
 // KV-cached decoder self-attention backward, "pull" form: the steps run T-1 -> 0; the call for step i records its coefficient
 // rows and writes row i of the K/V gradient complete (own term + the terms of the later steps, read from the Q / dO slabs),
 // so no K/V gradient row is ever read-modify-written and the slab needs no zero-fill.  s.Lk == step + 1.
-int mansy_attn_selfpull_ok(const AttnShape& s, int T);
 int mansy_launch_attn_bwd_selfpull(const float* Q_all, long long q_ts, const float* K, const float* V, const float* P_save,
                                    const float* dO_all, long long o_ts, float* dQ, float* dK, float* dV, float* dS_all, float* Pk_all,
-                                   const AttnShape& s, int T, int step, MansyDrop drop, hipStream_t st,
-                                   const float* img_f = nullptr, unsigned short* img_s = nullptr, int img_only = 0, int kv16 = 0);
+                                   const AttnShape& s, int T, int step, MansyDrop drop, hipStream_t st, AttnImage img = {});
 
 // ---------------------------------------------------------------- norms (norm.hip)
 // z = a (+ b);  y = LN(z) * w (+ bias).  z_out may be null (not saved) or alias a when b == null.

@@ -261,10 +261,12 @@ struct Eng {
   // K-tiles: d %% 256 == 0, d_ff %% 64 == 0, B %% 64 == 0; any other shape keeps the fp32-operand loops (same arithmetic, twice the traffic).
   bool s16 = false;
   unsigned short* im(const float* p) const { return s16 ? W.img + (p - W.fbase) : nullptr; }
+  // the attention launchers' view of the slab: rows kept as images only; kv16: the K/V cache (and the pull form's Q rows) read from the image
+  AttnImage attn_im(bool kv16 = false) const { return {W.fbase, im(W.fbase), 1, kv16 && s16 ? 1 : 0}; }
   bool s16_ok() const {
     return prec == 1 && d % 256 == 0 && d <= 1024 && f % 64 == 0 && B % 64 == 0 && S <= 10 && dh == 64 && H % 4 == 0 && mansy_dec_tail_ok(d, C6) != 0 &&
            mansy_ln_bwd_partial_ok(d) &&
-           mansy_attn_deferred_kv_ok(cross_shape(), T) != 0 && mansy_attn_selfpull_ok(self_shape(T - 1), T) != 0;
+           mansy_attn_deferred_kv_ok(cross_shape(), T) != 0 && mansy_attn_deferred_kv_ok(self_shape(T - 1), T) != 0;
   }
   MansyLnReduce ln_pending[LN_MULTI_MAX]; int ln_n_pending = 0;      // LayerNorm weight-gradient slot sets waiting for their reduce launch
   int flush_ln() {
@@ -412,7 +414,7 @@ struct Eng {
     for (int l = 0; l < c.n_enc; ++l) {
       const EncLayerP& p = P.enc[l]; EncBuf& e = W.enc[l];
       RC(lin_fwd(x, N, d, p.in_proj.w, p.in_proj.b, 3 * d, e.qkv, 0, mansy_no_drop()));
-      RC(mansy_launch_attn_fwd(e.qkv, e.qkv + d, e.qkv + 2 * d, e.ao, e.P, enc_shape(), dr(site_enc(l, 0), c.p_drop), st, W.fbase, im(W.fbase), 1));
+      RC(mansy_launch_attn_fwd(e.qkv, e.qkv + d, e.qkv + 2 * d, e.ao, e.P, enc_shape(), dr(site_enc(l, 0), c.p_drop), st, attn_im()));
       RC(lin_fwd(e.ao, N, d, p.out_proj.w, p.out_proj.b, d, e.z1, 0, dr(site_enc(l, 1), c.p_drop), x));          // z1 = x + drop(out_proj(ao))
       RC(ln_of(e.z1, p.n1, e.y1, e.m1, e.r1, N));
       RC(lin_fwd(e.y1, N, d, p.lin1.w, p.lin1.b, f, e.h, 1, dr(site_enc(l, 2), c.p_drop), nullptr, 2));
@@ -489,12 +491,12 @@ struct Eng {
       const float* mkv = e.memkv + (size_t)b0 * M * 2 * d;
       RC(lin_fwd(xi, nb, d, p.sa_in.w, p.sa_in.b, 3 * d, qkv_i, 0, mansy_no_drop(), nullptr, 1));      // + bf16 image: the K/V cache of the bf16-storage mode
       RC(mansy_launch_attn_fwd(qkv_i, kv0 + d, kv0 + 2 * d, e.ao1 + o * d, e.P1 + o * H * T, self_shape(i, nb),
-                               dr(site_dec(l, i, 0), c.p_drop, (size_t)b0 * H * (i + 1)), st, W.fbase, im(W.fbase), 1, s16 ? 1 : 0));
+                               dr(site_dec(l, i, 0), c.p_drop, (size_t)b0 * H * (i + 1)), st, attn_im(true)));
       RC(lin_fwd(e.ao1 + o * d, nb, d, p.sa_out.w, p.sa_out.b, d, e.z1 + o * d, 0, dr(site_dec(l, i, 1), c.p_drop, (size_t)b0 * d), xi));
       RC(ln_of(e.z1 + o * d, p.n1, e.y1 + o * d, e.m1 + o, e.r1 + o, nb));
       RC(lin_fwd(e.y1 + o * d, nb, d, p.ca_in.w, p.ca_in.b, d, e.qc + o * d, 0, mansy_no_drop()));
       RC(mansy_launch_attn_fwd(e.qc + o * d, mkv, mkv + d, e.ao2 + o * d, e.P2 + o * H * M, cross_shape(nb),
-                               dr(site_dec(l, i, 2), c.p_drop, (size_t)b0 * H * M), st, W.fbase, im(W.fbase), 1, s16 ? 1 : 0));
+                               dr(site_dec(l, i, 2), c.p_drop, (size_t)b0 * H * M), st, attn_im(true)));
       RC(lin_fwd(e.ao2 + o * d, nb, d, p.ca_out.w, p.ca_out.b, d, e.z2 + o * d, 0, dr(site_dec(l, i, 3), c.p_drop, (size_t)b0 * d), e.y1 + o * d));
       RC(ln_of(e.z2 + o * d, p.n2, e.y2 + o * d, e.m2 + o, e.r2 + o, nb));
       RC(lin_fwd(e.y2 + o * d, nb, d, p.lin1.w, p.lin1.b, f, e.h + o * f, 1, dr(site_dec(l, i, 4), c.p_drop, (size_t)b0 * f), nullptr, 2));
@@ -584,7 +586,7 @@ struct Eng {
         float* dao2_i = e.dao2 + o * d;
         RC(lin_dx(e.dbr2 + o * d, nb, d, p.ca_out.w, d, dao2_i, nullptr, nullptr, 1.f));   // d/dao2, kept for the deferred dV
         RC(mansy_launch_attn_bwd_dq(e.qc + o * d, mkv, mkv + d, e.P2 + o * H * M, dao2_i, e.dqc + o * d, e.dS2 + o * H * M,
-                                    e.Pk2 + o * H * M, cross_shape(nb), dr(site_dec(l, i, 2), c.p_drop, (size_t)b0 * H * M), st, W.fbase, im(W.fbase), 1, s16 ? 1 : 0));
+                                    e.Pk2 + o * H * M, cross_shape(nb), dr(site_dec(l, i, 2), c.p_drop, (size_t)b0 * H * M), st, attn_im(true)));
       } else {
         float* dmkv = e.dmemkv + (size_t)b0 * M * 2 * d;
         RC(lin_dx(e.dbr2 + o * d, nb, d, p.ca_out.w, d, gt, nullptr, nullptr, 1.f));       // gt = d/dao2
@@ -603,7 +605,7 @@ struct Eng {
         const size_t co = (size_t)b0 * T * H * T;
         RC(mansy_launch_attn_bwd_selfpull(kv0, (long long)B * 3 * d, kv0 + d, kv0 + 2 * d, e.P1 + o * H * T, e.dao1 + (size_t)b0 * d, (long long)B * d,
                                           dqkv_i, dkv0 + d, dkv0 + 2 * d, e.dS1 + co, e.Pk1 + co, self_shape(i, nb), T, i,
-                                          dr(site_dec(l, i, 0), c.p_drop, (size_t)b0 * H * (i + 1)), st, W.fbase, im(W.fbase), 1, s16 ? 1 : 0));
+                                          dr(site_dec(l, i, 0), c.p_drop, (size_t)b0 * H * (i + 1)), st, attn_im(true)));
       } else {
         RC(lin_dx(e.dbr1 + o * d, nb, d, p.sa_out.w, d, gt, nullptr, nullptr, 1.f));       // gt = d/dao1
         RC(mansy_launch_attn_bwd(qkv_at(e, o), kv0 + d, kv0 + 2 * d, e.P1 + o * H * T, gt, dqkv_i, dkv0 + d, dkv0 + 2 * d,
@@ -628,7 +630,7 @@ struct Eng {
     const bool defer_cross = mansy_attn_deferred_kv_ok(cross_shape(), T) != 0;
     // Self-attention K/V gradients in pull form (same condition): row i of the gradient slab is written once, complete, by
     // the call for step i -- no read-modify-write of rows 0..i at every step, no zero-fill of the slab.
-    const bool pull_self = mansy_attn_selfpull_ok(self_shape(T - 1), T) != 0;
+    const bool pull_self = mansy_attn_deferred_kv_ok(self_shape(T - 1), T) != 0;
     for (int l = 0; l < c.n_dec; ++l) {
       if (!pull_self) MANSY_HIP_CHECK(hipMemsetAsync(W.dec[l].dqkv, 0, sizeof(float) * (size_t)TB * 3 * d, st));
       if (!defer_cross) MANSY_HIP_CHECK(hipMemsetAsync(W.dec[l].dmemkv, 0, sizeof(float) * (size_t)B * M * 2 * d, st));
@@ -695,7 +697,7 @@ struct Eng {
     for (int l = 0; l < c.n_dec; ++l) {      // the chain: K/V gradients of the memory -> their projection's gradients -> the memory gradient
       const DecLayerP& p = P.dec[l]; DecBuf& e = W.dec[l];
       if (defer_cross)
-        RC(mansy_launch_attn_kvgrad(e.qc, (long long)B * d, e.dao2, (long long)B * d, e.dS2, e.Pk2, e.dmemkv, e.dmemkv + d, cross_shape(), T, 0, st, W.fbase, im(W.fbase)));
+        RC(mansy_launch_attn_kvgrad(e.qc, (long long)B * d, e.dao2, (long long)B * d, e.dS2, e.Pk2, e.dmemkv, e.dmemkv + d, cross_shape(), T, 0, st, attn_im()));
       RC(lin_dw(e.dmemkv, W.mem, B * M, 2 * d, d, p.ca_in.gw + (size_t)d * d, p.ca_in.gb ? p.ca_in.gb + d : nullptr, defer_cross));      // (the per-step accumulating form of the K/V gradients keeps floats only)
       RC(lin_dx(e.dmemkv, B * M, 2 * d, p.ca_in.w + (size_t)d * d, d, W.dmem, l == 0 ? nullptr : W.dmem, nullptr, 1.f, 0, defer_cross));
     }
@@ -726,7 +728,7 @@ struct Eng {
       RC(lin_dw(gx, e.ao, N, d, d, p.out_proj.gw, p.out_proj.gb));
       RC(lin_dx(gx, N, d, p.out_proj.w, d, gt, nullptr, nullptr, 1.f));                        // gt = d/dao
       RC(mansy_launch_attn_bwd(e.qkv, e.qkv + d, e.qkv + 2 * d, e.P, gt, W.g_wide, W.g_wide + d, W.g_wide + 2 * d, enc_shape(),
-                               dr(site_enc(l, 0), c.p_drop), 0, st, W.fbase, im(W.fbase), 1));
+                               dr(site_enc(l, 0), c.p_drop), 0, st, attn_im()));
       RC(lin_dw(W.g_wide, x_in, N, 3 * d, d, p.in_proj.gw, p.in_proj.gb));
       RC(lin_dx(W.g_wide, N, 3 * d, p.in_proj.w, d, gx, gz, nullptr, 1.f));                    // gx = d/d(layer input)
     }
