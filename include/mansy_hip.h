@@ -323,6 +323,37 @@ int mansy_sim_drive_client(const mansy_env_tables* T, void* state, int n, const 
                            int network, int viewport, int window, double* history, int* count, int* best, float* best_total, int* versions,
                            float* qoe_parts, double* scalars, unsigned char* over, int auto_reset, void* stream);
 
+/* ------------------------------------------------------------------ batched simulator: the client's search over per-step budget schedules
+ * Candidate k of mansy_sim_drive / mansy_sim_drive_client plans all H chunks of its horizon under ONE budget, so a horizon only ranks K
+ * levels of aggressiveness.  Here a candidate is a SCHEDULE: one of F budget levels per step ("above the estimate now, below it on the
+ * next two chunks"), all F^H of them, as the reference's MPC expert compares its 15^H action sequences.
+ *   levels f64 [F].  K = F^H candidates in lexicographic order, step 0 the most significant digit: candidate k uses at step t the level
+ *   digit_t(k) = (k / F^(H-1-t)) % F, and
+ *     budget[i,k,t] = (throughput[i] * (double)T.chunk_length) * levels[digit_t(k)]      (two float64 multiplies, in that order).
+ * Schedule look-ahead = the bits of two existing calls: mansy_sim_allocate(budgets, weights = NULL, K, H) on those budgets, then
+ * mansy_sim_lookahead_client(plans, K, H, network == MANSY_SIM_NET_ESTIMATE ? throughput : NULL, viewport, ..) on its plans.  total f32
+ * [n,K] (nullable), steps i32 [n], best i32 [n] and best_total f32 [n] (both nullable) are that call's; level_plans i32 [n,F,H,64] and
+ * level_bytes i32 [n,F,H] (both nullable) are plans[i,k,t,:] / plan_bytes[i,k,t] of any k with digit_t(k) = f -- the allocation of a
+ * chunk depends on that chunk and its budget alone, so the F^H schedules hold only F x H distinct ones and the K x H plans are never
+ * made.  Every rule of the two calls holds: rows t >= steps[i] are zeros; a closed record gives zeros and best = 0; the first
+ * candidate with the strictly largest total wins and a NaN never does.  Where steps[i] < H the candidates that share their first
+ * steps[i] digits tie, so the trailing digits of the winner are 0.  throughput f64 [n] is required (the budgets need it) and, like
+ * `state`, only read.
+ * Schedule drive = mansy_sim_drive_client's five stages for D decisions with stages 1-3 replaced by the look-ahead above at the
+ * session's current estimate; best i32 [n,D] holds the schedule's index.  Stage 4 commits level_plans[digit_0(best)][0] on the truth
+ * and stage 5 is the harmonic-mean estimator on history / count, both unchanged, auto_reset and the estimate carried across episodes
+ * included.  With H = 1 the call returns the bits of mansy_sim_drive_client(fractions = levels, K = F, H = 1, ..).
+ * 1 <= F <= MANSY_SIM_SCHED_MAX_LEVELS, 1 <= H <= MANSY_SIM_MAX_HORIZON, F^H <= MANSY_SIM_MAX_CANDIDATES, n * F^H below 2^31,
+ * 1 <= D <= MANSY_SIM_DRIVE_MAX_DECISIONS, 1 <= window <= MANSY_SIM_EST_MAX_WINDOW, n >= 1 (one workgroup per session keeps the F x H
+ * plans as 8 KB of bytes, the F^H totals and the record on chip). */
+#define MANSY_SIM_SCHED_MAX_LEVELS 16
+int mansy_sim_lookahead_schedules(const mansy_env_tables* T, const void* state, int n, const double* levels, int F, int H,
+                                  const double* throughput, int network, int viewport, int* level_plans, int* level_bytes, float* total,
+                                  int* steps, int* best, float* best_total, void* stream);
+int mansy_sim_drive_schedules(const mansy_env_tables* T, void* state, int n, const double* levels, int F, int H, int D, double* throughput,
+                              int network, int viewport, int window, double* history, int* count, int* best, float* best_total,
+                              int* versions, float* qoe_parts, double* scalars, unsigned char* over, int auto_reset, void* stream);
+
 /* ------------------------------------------------------------------ MPC expert (demonstrations for behaviour cloning)
  * Replaces ExpertEnv._profile_viewport_qualities_sizes and ExpertEnv.choose_action (bitrate_selection/envs/
  * expert_env.py:126-181, 358-422) + ExpertSimulator.virtual_simulate_download_with_chunk_size /

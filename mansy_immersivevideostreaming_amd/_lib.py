@@ -117,6 +117,8 @@ _PROTOS = {
     'mansy_sim_drive': [P, P, c_int, P, c_int, c_int, c_int, P, P, P, P, P, P, P, c_int, P],
     'mansy_sim_lookahead_client': [P, P, c_int, P, c_int, c_int, P, c_int, P, P, P, P, P, P, P],
     'mansy_sim_drive_client': [P, P, c_int, P, c_int, c_int, c_int, P, c_int, c_int, c_int, P, P, P, P, P, P, P, P, c_int, P],
+    'mansy_sim_lookahead_schedules': [P, P, c_int, P, c_int, c_int, P, c_int, c_int, P, P, P, P, P, P, P],
+    'mansy_sim_drive_schedules': [P, P, c_int, P, c_int, c_int, c_int, P, c_int, c_int, c_int, P, P, P, P, P, P, P, P, c_int, P],
     'mansy_expert_profile': [P, P, c_int, P, P, P, P, P, P, P],
     'mansy_expert_choose_action': [P, P, c_int, c_int, P, P, P, P, P, P, P, P],
     'mansy_net_num_params': [c_int],

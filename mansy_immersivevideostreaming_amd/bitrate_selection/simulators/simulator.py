@@ -15,6 +15,8 @@ throughput)` runs that planner closed-loop -- budgets from a throughput estimate
 the estimate renewed -- for many decisions in one launch.  `lookahead` and `drive` are an oracle (the real trace and the ground-truth
 viewport of chunks not yet watched); `lookahead_client` and `drive_client` score the plans as a client that could be deployed has to --
 at a throughput estimate made from finished downloads and on the predicted viewport -- and commit on the truth.
+`lookahead_schedules` and `drive_schedules` are that client with a budget level PER STEP: every one of the F^H sequences of F levels
+over H chunks is a candidate (`schedule_digits` decodes a candidate's index), searched in one launch without materialising its plans.
 
 The session records are the environment's (`mansy_env_init` / `mansy_env_reset`), so sessions walk the catalogue exactly as the
 environments of `MANSYVecEnv` do.  A state buffer belongs either to a `MANSYVecEnv` or to a simulator, never both: the simulator keeps no
@@ -34,12 +36,32 @@ DRIVE_MAX_CANDIDATES, DRIVE_MAX_DECISIONS = 64, 256      # MANSY_SIM_DRIVE_MAX_C
 EST_MAX_WINDOW = 8                                        # MANSY_SIM_EST_MAX_WINDOW: the sample slots of the throughput estimator
 VIEWPORTS = {'gt': 0, 'pred': 1}                          # MANSY_SIM_VIEW_GT, MANSY_SIM_VIEW_PRED
 NETWORKS = {'trace': 0, 'estimate': 1}                    # MANSY_SIM_NET_TRACE, MANSY_SIM_NET_ESTIMATE
+SCHED_MAX_LEVELS = 16                                     # MANSY_SIM_SCHED_MAX_LEVELS: the budget levels of a schedule search
 
 
 def _choice(name, value, table):
     if not isinstance(value, str) or value not in table:
         raise MansyError(f'{name} must be one of {sorted(table)}, not {value!r}')
     return table[value]
+
+
+def _sched_shape(F, H):
+    """The checks the schedule calls share on the number of levels F and the horizon H; returns K = F^H."""
+    for name, x, hi in (('F', F, SCHED_MAX_LEVELS), ('horizon', H, MAX_HORIZON)):
+        if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or not 1 <= x <= hi:
+            raise MansyError(f'{name} must be an integer in 1..{hi}')
+    K = int(F) ** int(H)
+    if K > MAX_CANDIDATES:
+        raise MansyError(f'{F} levels over a horizon of {H} are F^H = {K} schedules: at most {MAX_CANDIDATES} are supported')
+    return K
+
+
+def schedule_digits(F, H):
+    """The digit table of a schedule search: int64 tensor [F^H, H] whose row k holds the level candidate k uses at every step,
+    (k // F^(H-1-t)) % F at step t -- step 0 is the most significant digit, the candidates are in lexicographic order."""
+    K = _sched_shape(F, H)
+    place = int(F) ** torch.arange(int(H) - 1, -1, -1, dtype=torch.int64)
+    return (torch.arange(K, dtype=torch.int64)[:, None] // place[None, :]) % int(F)
 
 
 class BatchedSimulator:
@@ -81,6 +103,8 @@ class BatchedSimulator:
         self._drive = {}                      # (K, H, D) -> drive()'s buffers and the two namespaces over them
         self._look_client = {}                # (K, H) -> lookahead_client()'s buffers, its own
         self._drive_client = {}               # (K, H, D) -> drive_client()'s buffers, its own
+        self._look_sched = {}                 # (F, H) -> lookahead_schedules()'s buffers
+        self._drive_sched = {}                # (F, H, D) -> drive_schedules()'s buffers, its own
         # the throughput estimator of drive_client(): eight sample slots per session (the newest last) and how many are filled
         self.history = torch.zeros(self.n, EST_MAX_WINDOW, **f64)
         self.count = torch.zeros(self.n, dtype=torch.int32, device=dev)
@@ -353,6 +377,87 @@ class BatchedSimulator:
                                            int(bool(auto_reset)), stream_ptr(self.device)), 'mansy_sim_drive_client')
         return out
 
+    def _sched_arguments(self, levels, horizon, throughput):
+        """The argument checks `lookahead_schedules` and `drive_schedules` share; returns F, H and K = F^H."""
+        if not isinstance(levels, torch.Tensor) or levels.dtype != torch.float64:
+            raise MansyError('levels must be a float64 cuda tensor (there is no CPU path)')
+        if not isinstance(throughput, torch.Tensor) or throughput.dtype != torch.float64:
+            raise MansyError('throughput must be a float64 cuda tensor (there is no CPU path)')
+        if levels.dim() != 1:
+            raise MansyError(f'levels must have the shape [F], not {list(levels.shape)}')
+        if tuple(throughput.shape) != (self.n,):
+            raise MansyError(f'throughput must have the shape [{self.n}], not {list(throughput.shape)}')
+        F = int(levels.shape[0])
+        if not 1 <= F <= SCHED_MAX_LEVELS:
+            raise MansyError(f'levels holds F = {F} budget levels: 1..{SCHED_MAX_LEVELS} are supported')
+        K = _sched_shape(F, horizon)
+        if self.n * K >= 2 ** 31:
+            raise MansyError('n * F^H must stay below 2^31')
+        return F, int(horizon), K
+
+    def lookahead_schedules(self, levels, horizon, throughput, network='estimate', viewport='pred', per_leaf=True):
+        """The client's look-ahead over BUDGET SCHEDULES (mansy_sim_lookahead_schedules): candidate k of the K = F^horizon candidates
+        plans chunk next_chunk + t under the byte budget throughput[i] x chunk_length x levels[digit_t(k)], its digits being row k of
+        `schedule_digits(F, horizon)`.  The call returns the bits of `allocate` on those budgets [n,K,H] followed by
+        `lookahead_client(plans, throughput if network == 'estimate' else None, viewport, per_step=False)`, without making the K x H
+        plans: a schedule's plan for a chunk depends on its level there alone, so F x H allocations serve all of them.  The sessions
+        do not move.
+        levels: float64 cuda tensor [F], 1 <= F <= SCHED_MAX_LEVELS, F^horizon <= MAX_CANDIDATES; throughput: float64 cuda tensor [n].
+        Returns a namespace of device tensors, without a synchronisation: total f32 [n,K] (only with per_leaf), steps i32 [n], best i32
+        [n], best_total f32 [n], level_plans i32 [n,F,H,64] and level_bytes i32 [n,F,H] (the plan and its size of every schedule that
+        uses level f at step t; rows t >= steps[i] are zeros).  Where steps[i] < horizon the schedules that share their first steps[i]
+        digits tie and the first wins: the trailing digits of best are 0.  The buffers are cached per (F, horizon)."""
+        F, H, K = self._sched_arguments(levels, horizon, throughput)
+        view, net = _choice('viewport', viewport, VIEWPORTS), _choice('network', network, NETWORKS)
+        for name, x in (('levels', levels), ('throughput', throughput)):
+            if not x.is_cuda or x.device != self.state.device or not x.is_contiguous():
+                raise MansyError(f'{name} must be a contiguous float64 cuda tensor on {self.state.device} (there is no CPU path)')
+        b = self._look_sched.get((F, H))
+        if b is None:
+            dev = self.device
+            short = types.SimpleNamespace(steps=torch.zeros(self.n, dtype=torch.int32, device=dev), best=torch.zeros(self.n, dtype=torch.int32, device=dev),
+                                          best_total=torch.zeros(self.n, dtype=torch.float32, device=dev),
+                                          level_plans=torch.zeros(self.n, F, H, N_TILE, dtype=torch.int32, device=dev),
+                                          level_bytes=torch.zeros(self.n, F, H, dtype=torch.int32, device=dev))
+            b = types.SimpleNamespace(total=None, short=short, full=None)
+            self._look_sched[(F, H)] = b
+        if per_leaf and b.full is None:
+            b.total = torch.zeros(self.n, K, dtype=torch.float32, device=self.device)
+            b.full = types.SimpleNamespace(total=b.total, **vars(b.short))
+        out = b.full if per_leaf else b.short
+        check(lib().mansy_sim_lookahead_schedules(ctypes.byref(self.tables.c), ptr(self.state), self.n, ptr(levels), F, H, ptr(throughput), net, view,
+                                                  ptr(out.level_plans), ptr(out.level_bytes), ptr(b.total) if per_leaf else None, ptr(out.steps),
+                                                  ptr(out.best), ptr(out.best_total), stream_ptr(self.device)), 'mansy_sim_lookahead_schedules')
+        return out
+
+    def drive_schedules(self, levels, horizon, decisions, throughput, window=5, viewport='pred', network='estimate', auto_reset=False,
+                        per_tile=True):
+        """`drive_client` with the schedule search in the place of its K candidates (mansy_sim_drive_schedules): per decision and
+        session `lookahead_schedules` at the current estimate picks the best of the F^horizon budget schedules, the plan of its FIRST
+        level for the next chunk is committed on the truth and the estimator is renewed, all as `drive_client` does it, auto_reset and
+        the estimator carried across episodes included.  With horizon=1 the call returns `drive_client(levels, 1, ...)`'s bits.
+        levels: float64 cuda tensor [F] as in `lookahead_schedules`; the other arguments are `drive_client`'s.  Returns `drive_client`'s
+        namespace in buffers of its own, cached per (F, horizon, decisions), without a synchronisation: best i32 [n,D] is the schedule's
+        index, and first_level i64 [n,D] = best // F^(horizon-1) the level it commits."""
+        F, H, K = self._sched_arguments(levels, horizon, throughput)
+        for name, x, hi in (('decisions', decisions, DRIVE_MAX_DECISIONS), ('window', window, EST_MAX_WINDOW)):
+            if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or not 1 <= x <= hi:
+                raise MansyError(f'{name} must be an integer in 1..{hi}')
+        D = int(decisions)
+        view, net = _choice('viewport', viewport, VIEWPORTS), _choice('network', network, NETWORKS)
+        for name, x in (('levels', levels), ('throughput', throughput)):
+            if not x.is_cuda or x.device != self.state.device or not x.is_contiguous():
+                raise MansyError(f'{name} must be a contiguous float64 cuda tensor on {self.state.device} (there is no CPU path)')
+        if auto_reset and getattr(self.tables, 'unvisitable', None):
+            raise MansyError('auto_reset walks the whole catalogue, but some of its entries hold no tables (negative slots in `samples`)')
+        b, out = self._drive_buffers(self._drive_sched, F, H, D, per_tile, throughput, history=self.history, count=self.count)
+        check(lib().mansy_sim_drive_schedules(ctypes.byref(self.tables.c), ptr(self.state), self.n, ptr(levels), F, H, D, ptr(throughput), net, view,
+                                              int(window), ptr(self.history), ptr(self.count), ptr(out.best), ptr(out.best_total),
+                                              ptr(b.versions) if per_tile else None, ptr(out.qoe_parts), ptr(out.scalars), ptr(out.over),
+                                              int(bool(auto_reset)), stream_ptr(self.device)), 'mansy_sim_drive_schedules')
+        out.first_level = out.best.long() // F ** (H - 1)
+        return out
+
     def simulate_download(self, tile_rates, auto_reset=False, validate=False):
         """tile_rates: int32 cuda tensor [n,64], bitrate VERSION 0..4 per tile (values outside are clamped by the kernel; validate=True
         raises instead, at the cost of one synchronisation).  Returns a namespace of device tensors: tile_size, tile_quality [n,64] f32,
@@ -564,6 +669,44 @@ class Simulator:
         out = self._sim.drive_client(dev_f, horizon, decisions, dev_thr, window=window, viewport=viewport, network=network)
         self._mirror_driven(out, int(decisions))
         self.driven.history, self.driven.count = out.history[0].cpu().numpy(), int(out.count[0].item())
+        return float(dev_thr[0].item())
+
+    def _levels(self, levels, horizon, throughput):
+        """The array arguments of the two schedule calls as device tensors: levels [F] and the estimate [1]."""
+        try:
+            f = np.asarray(levels)
+            thr = float(throughput)
+        except Exception as e:
+            raise MansyError(f'levels must be array-like [F] and throughput a number: {e}')
+        if f.ndim != 1 or f.dtype.kind not in 'fiu' or not 1 <= f.shape[0] <= SCHED_MAX_LEVELS:
+            raise MansyError(f'levels must be numbers [F] with 1 <= F <= {SCHED_MAX_LEVELS}')
+        _sched_shape(int(f.shape[0]), horizon)
+        return (torch.from_numpy(np.ascontiguousarray(f, dtype=np.float64)).to(self.device),
+                torch.tensor([thr], dtype=torch.float64, device=self.device))
+
+    def lookahead_schedules(self, levels, horizon, throughput, network='estimate', viewport='pred'):
+        """The F^horizon budget schedules of `levels` (array-like [F] of numbers) scored from where the session stands
+        (BatchedSimulator.lookahead_schedules); the session does not move.  throughput: a number (bytes/s).  Returns a namespace: total
+        float32 [F^horizon], steps (int), best (int; `schedule_digits` decodes it), best_total (float), level_plans int32 [F,H,64] and
+        level_bytes int32 [F,H] (rows t >= steps are zeros)."""
+        _choice('viewport', viewport, VIEWPORTS), _choice('network', network, NETWORKS)
+        dev_f, dev_thr = self._levels(levels, horizon, throughput)
+        out = self._sim.lookahead_schedules(dev_f, horizon, dev_thr, network=network, viewport=viewport)
+        return types.SimpleNamespace(total=out.total[0].cpu().numpy(), steps=int(out.steps[0].item()), best=int(out.best[0].item()),
+                                     best_total=float(out.best_total[0].item()), level_plans=out.level_plans[0].cpu().numpy(),
+                                     level_bytes=out.level_bytes[0].cpu().numpy())
+
+    def drive_schedules(self, levels, horizon, decisions, throughput, window=5, viewport='pred', network='estimate'):
+        """`drive_client` over budget schedules (BatchedSimulator.drive_schedules without auto_reset): levels array-like [F] of numbers.
+        Returns the new estimate as a float; the decisions' outputs stay in `self.driven` as `drive_client` leaves them (best holds the
+        schedule's index), plus first_level int64 [D]."""
+        if self.next_chunk > self.end_chunk:
+            raise MansyError(f'the session is over (next chunk {self.next_chunk} > end chunk {self.end_chunk})')
+        dev_f, dev_thr = self._levels(levels, horizon, throughput)
+        out = self._sim.drive_schedules(dev_f, horizon, decisions, dev_thr, window=window, viewport=viewport, network=network)
+        self._mirror_driven(out, int(decisions))
+        self.driven.history, self.driven.count = out.history[0].cpu().numpy(), int(out.count[0].item())
+        self.driven.first_level = out.first_level[0].cpu().numpy()
         return float(dev_thr[0].item())
 
     def _mirror_driven(self, out, decisions):

@@ -26,6 +26,10 @@
 // ground-truth viewport of chunks not yet watched).  The same helpers, instantiated for a network model that divides the chunk size by
 // a throughput estimate and pointed at the predicted map, score plans as a deployable client has to; the driving kernel then keeps a
 // window of throughput samples per session and commits on the truth all the same.
+// Budget schedules (mansy_sim_lookahead_schedules / mansy_sim_drive_schedules): a candidate takes one of F budget levels per step, all
+// F^H sequences.  The allocation of a chunk depends on the chunk and its budget alone and everything tile-wide in a virtual step on
+// that plan alone, so a workgroup makes F x H plans and step profiles with a wave each and walks the schedules with a LANE each, on
+// the scalar half of the virtual step; the results are the bits of mansy_sim_allocate + mansy_sim_lookahead_client on the F^H x H plans.
 #include "mansy_kernels.h"
 #include "../../include/mansy_hip.h"
 
@@ -211,15 +215,32 @@ struct LookConst { const double* bw; int tlen; float w0, w1, w2, max_rate; doubl
 // division by the bytes/s the caller believes in (a client's; the trace position of the record is then not read).
 constexpr int NET_TRACE = MANSY_SIM_NET_TRACE, NET_ESTIMATE = MANSY_SIM_NET_ESTIMATE;
 
-// One virtual step by one wavefront (lane = tile): sim_download_kernel's arithmetic from "Simulator.simulate_download" to the QoE, line
-// for line, on the tile's size / quality of the planned version and the chunk's viewport map gv (ground truth or prediction).  With
-// NET_ESTIMATE the trace walk alone is replaced: download_time = chunk_size / c.rate in plain IEEE double, whatever c.rate holds.
-// qoe_row / sc_row: this step's four-value output rows (nullable, launch-uniform).
+// One virtual step is sim_download_kernel's arithmetic from "Simulator.simulate_download" to the QoE, line for line, in a tile-wide part
+// and a scalar part.  The tile-wide part, by one wavefront (lane = tile) on the tile's size / quality of the planned version and the
+// chunk's viewport map gv (ground truth or prediction): what the step has of the chunk and its plan alone, the same in every lane --
+// the integer chunk size (wave_isum), and the viewport quality (qoe1) with the intra-chunk variance (look_quality).
+struct StepProfile { int chunk_size; float vq, intra; };
+__device__ __forceinline__ void look_quality(StepProfile& p, float tq, float gv, float max_rate) {
+  const ViewportSums vs = viewport_sums(gv, tq);
+  const float s_v = vs.s_v;
+  const float vq = vs.s_vq / s_v;
+  const float s_var = var_sum(vs, gv, tq, vq);
+  p.intra = (s_var / s_v) / max_rate;
+  p.vq = vq / max_rate;
+}
+__device__ __forceinline__ StepProfile look_profile(int my_size, float tq, float gv, float max_rate) {
+  StepProfile p;
+  p.chunk_size = wave_isum(my_size);
+  look_quality(p, tq, gv, max_rate);
+  return p;
+}
+// The scalar part, on the state the candidate carries from step to step: the download (the walk over the trace, or with NET_ESTIMATE
+// download_time = chunk_size / c.rate in plain IEEE double, whatever c.rate holds) with the buffer rule (look_download), then
+// |vq - prev_vq|, the QoE and the float32 running total (look_score).  Nothing here looks at a tile, so a single lane may run it on a
+// profile another wave made (the schedule search).
+struct StepScalars { double download_time, rebuf; float qoe, qoe3; };
 template <int NET>
-__device__ __forceinline__ void look_step(LookState& s, const LookConst& c, int my_size, float tq, float gv, int lane, float* qoe_row,
-                                          double* sc_row) {
-  const int chunk_size = wave_isum(my_size);
-  double download_time;
+__device__ __forceinline__ void look_download(LookState& s, const LookConst& c, int chunk_size, StepScalars& r) {
   if constexpr (NET == NET_TRACE) {
     const double start = s.cur_time;
     double size = (double)chunk_size;
@@ -229,29 +250,43 @@ __device__ __forceinline__ void look_step(LookState& s, const LookConst& c, int 
       if (size >= remain) { s.cur_idx = s.cur_idx + 1 == c.tlen ? 0 : s.cur_idx + 1; s.bwc = c.bw[s.cur_idx]; s.cur_time = fl; size -= remain; }
       else { s.cur_time += size / s.bwc; size = 0; }
     }
-    download_time = s.cur_time - start;
+    r.download_time = s.cur_time - start;
   } else {
-    download_time = (double)chunk_size / c.rate;
+    r.download_time = (double)chunk_size / c.rate;
   }
-  double rebuf = 0.0;
-  if (download_time > s.buf_size) { rebuf = download_time - s.buf_size; s.buf_size = c.chunk_length; }
-  else s.buf_size = s.buf_size - download_time + c.chunk_length;
-  const ViewportSums vs = viewport_sums(gv, tq);
-  const float s_v = vs.s_v;
-  float vq = vs.s_vq / s_v;
-  const float s_var = var_sum(vs, gv, tq, vq);
-  const float intra = (s_var / s_v) / c.max_rate;
-  vq = vq / c.max_rate;
-  const float inter = s.has_prev ? fabsf(vq - s.prev_vq) : 0.f;
-  s.prev_vq = vq; s.has_prev = 1;
-  const float qoe1 = vq, qoe3 = intra + inter;
-  const float qoe = c.w0 * qoe1 - c.w1 * (float)rebuf - c.w2 * qoe3;
-  s.sum = s.sum + qoe;                       // ((0 + qoe_0) + qoe_1) + .. : plan_step's ps.sum (env.hip)
+  r.rebuf = 0.0;
+  if (r.download_time > s.buf_size) { r.rebuf = r.download_time - s.buf_size; s.buf_size = c.chunk_length; }
+  else s.buf_size = s.buf_size - r.download_time + c.chunk_length;
+}
+__device__ __forceinline__ void look_score(LookState& s, const LookConst& c, const StepProfile& p, StepScalars& r) {
+  const float inter = s.has_prev ? fabsf(p.vq - s.prev_vq) : 0.f;
+  s.prev_vq = p.vq; s.has_prev = 1;
+  r.qoe3 = p.intra + inter;
+  r.qoe = c.w0 * p.vq - c.w1 * (float)r.rebuf - c.w2 * r.qoe3;
+  s.sum = s.sum + r.qoe;                     // ((0 + qoe_0) + qoe_1) + .. : plan_step's ps.sum (env.hip)
+}
+template <int NET>
+__device__ __forceinline__ void look_scalars(LookState& s, const LookConst& c, const StepProfile& p) {
+  StepScalars r;
+  look_download<NET>(s, c, p.chunk_size, r);
+  look_score(s, c, p, r);
+}
+// One virtual step by one wavefront: the two parts, their halves in the order of the committed step (size, download, quality, score).
+// qoe_row / sc_row: this step's four-value output rows (nullable, launch-uniform).
+template <int NET>
+__device__ __forceinline__ void look_step(LookState& s, const LookConst& c, int my_size, float tq, float gv, int lane, float* qoe_row,
+                                          double* sc_row) {
+  StepProfile p;
+  StepScalars r;
+  p.chunk_size = wave_isum(my_size);
+  look_download<NET>(s, c, p.chunk_size, r);
+  look_quality(p, tq, gv, c.max_rate);
+  look_score(s, c, p, r);
   if (sc_row) {
     const double chunk_quality = seq_dsum64(tq);
-    if (lane == 0) { sc_row[0] = (double)chunk_size; sc_row[1] = chunk_quality; sc_row[2] = download_time; sc_row[3] = rebuf; }
+    if (lane == 0) { sc_row[0] = (double)p.chunk_size; sc_row[1] = chunk_quality; sc_row[2] = r.download_time; sc_row[3] = r.rebuf; }
   }
-  if (qoe_row && lane == 0) { qoe_row[0] = qoe; qoe_row[1] = qoe1; qoe_row[2] = (float)rebuf; qoe_row[3] = qoe3; }
+  if (qoe_row && lane == 0) { qoe_row[0] = r.qoe; qoe_row[1] = p.vq; qoe_row[2] = (float)r.rebuf; qoe_row[3] = r.qoe3; }
 }
 
 struct LookTile { int size; float quality, gv; };
@@ -282,6 +317,26 @@ __device__ __forceinline__ SessionView view_of(const Rec& r) {
 struct PlanRows { const int* p; __device__ __forceinline__ int operator()(int t) const { return p[(size_t)t * NTL]; } };
 struct PlanBytes { const unsigned char* p; __device__ __forceinline__ int operator()(int t) const { return p[t * NTL]; } };
 
+// What the virtual steps of a session share (the trace, the QoE weights, rate: the bytes/s of NET_ESTIMATE) and the state a candidate
+// starts from: where the record stands, an empty total.
+template <int NET>
+__device__ __forceinline__ LookConst look_const(const mansy_env_tables& T, const SessionView& r, double rate) {
+  const float* w = T.qoe_w + 3 * r.qoe;
+  LookConst c;
+  if constexpr (NET == NET_TRACE) { c.bw = T.trace_bw + (size_t)r.trace * T.trace_len_max; c.tlen = T.trace_len[r.trace]; }
+  else { c.bw = nullptr; c.tlen = 0; }
+  c.rate = rate;
+  c.w0 = w[0]; c.w1 = w[1]; c.w2 = w[2]; c.max_rate = (float)T.video_rates[NR - 1]; c.chunk_length = (double)T.chunk_length;
+  return c;
+}
+template <int NET>
+__device__ __forceinline__ LookState look_start(const SessionView& r, const LookConst& c) {
+  LookState s;
+  s.cur_time = r.cur_time; s.buf_size = r.buf_size; s.cur_idx = r.cur_idx; s.has_prev = r.has_prev; s.prev_vq = r.prev_vq; s.sum = 0.f;
+  s.bwc = NET == NET_TRACE ? c.bw[s.cur_idx] : 0.0;
+  return s;
+}
+
 // One candidate walked by one wavefront (lane = tile) over steps >= 1 chunks from where the session stands; returns the float32 total.
 // The loads of step t + 1 depend on t alone, not on the download of step t, so they are issued before that step's dependent chain
 // (trace walk, sequential sums) instead of behind it.  qoe_parts / scalars: the candidate's [H,4] rows (nullable, launch-uniform).
@@ -290,15 +345,8 @@ template <int NET, typename Plan>
 __device__ __forceinline__ float look_walk(const mansy_env_tables& T, const SessionView& r, int steps, const Plan& plan, int lane, double rate,
                                            const unsigned char* __restrict__ vmap, float* qoe_parts, double* scalars) {
   const int chunk = r.next_chunk;
-  const float* w = T.qoe_w + 3 * r.qoe;
-  LookConst c;
-  if constexpr (NET == NET_TRACE) { c.bw = T.trace_bw + (size_t)r.trace * T.trace_len_max; c.tlen = T.trace_len[r.trace]; }
-  else { c.bw = nullptr; c.tlen = 0; }
-  c.rate = rate;
-  c.w0 = w[0]; c.w1 = w[1]; c.w2 = w[2]; c.max_rate = (float)T.video_rates[NR - 1]; c.chunk_length = (double)T.chunk_length;
-  LookState s;
-  s.cur_time = r.cur_time; s.buf_size = r.buf_size; s.cur_idx = r.cur_idx; s.has_prev = r.has_prev; s.prev_vq = r.prev_vq; s.sum = 0.f;
-  s.bwc = NET == NET_TRACE ? c.bw[s.cur_idx] : 0.0;
+  const LookConst c = look_const<NET>(T, r, rate);
+  LookState s = look_start<NET>(r, c);
   const size_t mrow = manifest_row(T, r.video, chunk) + lane;
   const size_t vrow = viewport_cell(T, r.vp, chunk) * NTL + lane;
   LookTile next = look_load(T, vmap, plan(0), mrow, vrow, 0);
@@ -556,8 +604,16 @@ struct DriveShared {
 constexpr int DRIVE_WIDE_SESSIONS = 256;   // up to one session per CU of an MI355X: the wide workgroup
 // The client's loop (mansy_sim_drive_client) keeps the session's throughput samples beside the record: the newest at index 7.
 struct DriveSharedClient : DriveShared { double history[MANSY_SIM_EST_MAX_WINDOW]; int count; };
-struct DriveOracle { using Shared = DriveShared; static constexpr bool client = false; };
-struct DriveClient { using Shared = DriveSharedClient; static constexpr bool client = true; };
+// The schedule search (mansy_sim_lookahead_schedules / mansy_sim_drive_schedules) keeps what the F^H schedules are made of: the F x H
+// plans as bytes, [f][t][tile], and the step profile of every one of them.
+constexpr int SCHED_STEPS = MANSY_SIM_SCHED_MAX_LEVELS * MANSY_SIM_MAX_HORIZON;
+struct SchedShared : DriveSharedClient {
+  unsigned char plans[SCHED_STEPS * NTL];
+  int chunk_size[SCHED_STEPS]; float vq[SCHED_STEPS], intra[SCHED_STEPS];
+};
+struct DriveOracle { using Shared = DriveShared; static constexpr bool client = false, schedules = false; };
+struct DriveClient { using Shared = DriveSharedClient; static constexpr bool client = true, schedules = false; };
+struct DriveSchedules { using Shared = SchedShared; static constexpr bool client = true, schedules = true; };
 
 // The estimator of mansy_sim_drive_client after a committed step with download_time > 0, by ONE lane on the slots in LDS: the slots
 // shift down by one, the sample goes in at the top, and the estimate is the harmonic mean of the newest min(window, count) samples,
@@ -574,9 +630,136 @@ __device__ __forceinline__ double estimate_push(double* history, int& count, dou
   return (double)m / sum;
 }
 
+// The allocations of one decision by the WAVES wavefronts of a session's workgroup: plans[(k * H + t) * 64 + tile] for K budgets
+// per_chunk * fractions[k] over the `steps` chunks the session has ahead.  The candidate with the largest budget leads: one wave per
+// chunk records its rounds, the others go on from the rounds they share.  TWO BARRIERS, reached by every wave: one after the leading
+// allocations, one after the rest.
+template <int WAVES>
+__device__ __forceinline__ void drive_allocate(const mansy_env_tables& T, const SessionView& v, int steps, double per_chunk,
+                                               const double* __restrict__ fractions, int K, int H, unsigned char* plans, DriveShared& sh, int wave,
+                                               int lane) {
+  int lead_k = 0;
+  double lead = per_chunk * fractions[0];
+  for (int k = 1; k < K; ++k) {
+    const double budget = per_chunk * fractions[k];
+    if (__ballot(budget > lead) != 0ull) { lead = budget; lead_k = k; }
+  }
+  for (int t = wave; t < steps; t += WAVES) {
+    const AllocTile a = alloc_tile(T, v.video, v.vp, v.next_chunk + t, nullptr, lane);
+    int ver = 0, total = a.base;
+    const int rounds = alloc_rounds(a, lead, lane, 0, ver, total, sh.rec_win[t], sh.rec_total[t]);
+    if (lane == 0) sh.rounds[t] = rounds;
+    plans[(lead_k * H + t) * NTL + lane] = (unsigned char)ver;
+  }
+  __syncthreads();
+  const int KS = K * steps;
+  for (int kt = wave; kt < KS; kt += WAVES) {
+    const int k = kt / steps, t = kt - k * steps;
+    if (k == lead_k) continue;
+    const double budget = per_chunk * fractions[k];
+    const AllocTile a = alloc_tile(T, v.video, v.vp, v.next_chunk + t, nullptr, lane);
+    int ver, total;
+    const int round = alloc_resume(a, budget, lead, lane, sh.rec_win[t], sh.rec_total[t], __builtin_amdgcn_readfirstlane(sh.rounds[t]), ver, total);
+    alloc_rounds(a, budget, lane, round, ver, total, nullptr, nullptr);
+    plans[(k * H + t) * NTL + lane] = (unsigned char)ver;
+  }
+  __syncthreads();
+}
+
+// The F^steps schedule prefixes of a session walked with a lane per prefix on the step profiles in LDS: prefix p uses at step t the
+// level (p / F^(steps-1-t)) % F, and its float32 total goes to totals[p].  The lanes of a wave diverge in the trace walk's loop.
+template <int NET>
+__device__ __forceinline__ void sched_walk(const mansy_env_tables& T, const SessionView& v, int steps, int P, int F, int H, double rate,
+                                           const SchedShared& sh, float* totals, int thread, int threads) {
+  if (P == 0) return;                         // a closed record (the same in every thread; no barrier in here)
+  const LookConst c = look_const<NET>(T, v, rate);
+  const LookState start = look_start<NET>(v, c);
+  for (int p = thread; p < P; p += threads) {
+    LookState s = start;
+    int place = P / F;                        // F^(steps-1-t)
+    for (int t = 0; t < steps; ++t) {
+      const int ft = (p / place) % F * H + t;
+      place = place / F;
+      StepProfile q;
+      q.chunk_size = sh.chunk_size[ft]; q.vq = sh.vq[ft]; q.intra = sh.intra[ft];
+      look_scalars<NET>(s, c, q);
+    }
+    totals[p] = s.sum;
+  }
+}
+
+// The schedule search of one session by its workgroup at the estimate thr: the F x steps allocations under thr x chunk_length x
+// levels[f] into sh.plans (drive_allocate), one wave per (f, t) for the step profile of that plan on vmap, then the walks.  Returns
+// P = F^steps, the number of prefixes that differ (0 for a closed record), with totals[0 .. P) filled: the F^H schedules that share a
+// prefix share its total, and the first of them is F^(H-steps) x the prefix.  FOUR BARRIERS, reached by every wave, the last one
+// behind the walks.
+template <int WAVES>
+__device__ __forceinline__ int sched_search(const mansy_env_tables& T, const SessionView& v, int steps, double thr, const double* __restrict__ levels,
+                                            int F, int H, int network, const unsigned char* __restrict__ vmap, SchedShared& sh, float* totals,
+                                            int wave, int lane) {
+  drive_allocate<WAVES>(T, v, steps, thr * (double)T.chunk_length, levels, F, H, sh.plans, sh, wave, lane);
+  const int FS = F * steps;
+  for (int ft = wave; ft < FS; ft += WAVES) {
+    const int f = ft / steps, t = ft - f * steps;
+    const size_t mrow = manifest_row(T, v.video, v.next_chunk) + lane;
+    const size_t vrow = viewport_cell(T, v.vp, v.next_chunk) * NTL + lane;
+    const LookTile x = look_load(T, vmap, sh.plans[(f * H + t) * NTL + lane], mrow, vrow, t);
+    const StepProfile p = look_profile(x.size, x.quality, x.gv, (float)T.video_rates[NR - 1]);
+    if (lane == 0) { sh.chunk_size[f * H + t] = p.chunk_size; sh.vq[f * H + t] = p.vq; sh.intra[f * H + t] = p.intra; }
+  }
+  __syncthreads();
+  int P = steps > 0 ? 1 : 0;
+  for (int t = 0; t < steps; ++t) P *= F;
+  const int thread = wave * NTL + lane;
+  if (network == NET_ESTIMATE) sched_walk<NET_ESTIMATE>(T, v, steps, P, F, H, thr, sh, totals, thread, WAVES * NTL);   // (a kernel argument)
+  else sched_walk<NET_TRACE>(T, v, steps, P, F, H, 0.0, sh, totals, thread, WAVES * NTL);
+  __syncthreads();
+  return P;
+}
+
+// One workgroup per session, as the driving kernel below; the record is only read.  totals: dynamic LDS, F^H floats.
+template <int WAVES>
+__global__ __launch_bounds__(WAVES * 64) void sim_lookahead_schedules_kernel(mansy_env_tables T, const EnvState* __restrict__ st,
+                                                                             const double* __restrict__ levels, int F, int H, int K,
+                                                                             const double* __restrict__ throughput, int network,
+                                                                             const unsigned char* __restrict__ vmap, int* level_plans, int* level_bytes,
+                                                                             float* total, int* steps_out, int* best, float* best_total) {
+  extern __shared__ __align__(16) unsigned char sched_lds[];
+  __shared__ SchedShared sh;
+  float* totals = (float*)sched_lds;
+  const int e = blockIdx.x, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  SessionView v = view_of(st[e]);             // the same values in every lane of the workgroup; the integers into scalar registers
+  v.video = __builtin_amdgcn_readfirstlane(v.video); v.vp = __builtin_amdgcn_readfirstlane(v.vp);
+  v.trace = __builtin_amdgcn_readfirstlane(v.trace); v.qoe = __builtin_amdgcn_readfirstlane(v.qoe);
+  v.next_chunk = __builtin_amdgcn_readfirstlane(v.next_chunk); v.end_chunk = __builtin_amdgcn_readfirstlane(v.end_chunk);
+  v.cur_idx = __builtin_amdgcn_readfirstlane(v.cur_idx); v.has_prev = __builtin_amdgcn_readfirstlane(v.has_prev);
+  const int steps = steps_ahead(T, v.next_chunk, v.end_chunk, H);
+  const int P = sched_search<WAVES>(T, v, steps, throughput[e], levels, F, H, network, vmap, sh, totals, wave, lane);
+  const int leaves = P > 0 ? K / P : K;        // the schedules that share a prefix: F^(H-steps)
+  if (wave == 0) {
+    const int b = P > 0 ? best_of(totals, P, lane) : 0;
+    if (lane == 0) {
+      steps_out[e] = steps;
+      if (best) best[e] = b * leaves;
+      if (best_total) best_total[e] = P > 0 ? totals[b] : 0.f;
+    }
+  }
+  if (total)
+    for (int k = wave * NTL + lane; k < K; k += WAVES * NTL) total[(size_t)e * K + k] = P > 0 ? totals[k / leaves] : 0.f;
+  for (int ft = wave; ft < F * H; ft += WAVES) {   // rows t >= steps: zeros
+    const int t = ft % H;
+    const size_t row = (size_t)e * F * H + ft;
+    if (level_plans) level_plans[row * NTL + lane] = t < steps ? sh.plans[ft * NTL + lane] : 0;
+    if (level_bytes && lane == 0) level_bytes[row] = t < steps ? sh.chunk_size[ft] : 0;
+  }
+}
+
 // Model::client == false is mansy_sim_drive: the look-ahead on the trace and the ground truth, the last sample as the estimate; the
 // arguments from `network` on are not read.  true: the look-ahead scores on vmap with the network model `network`, and the estimate
 // comes from the window of samples (history f64 [n,8], count i32 [n], in and out).
+// Model::schedules (mansy_sim_drive_schedules): the client's loop with fractions = the K budget levels, one of which every step of a
+// candidate takes: sched_search stands in for the allocations and the walks, wave 0 scans the totals of the prefixes and commits the
+// first step of the winner's first level.  The dynamic LDS is then K^H totals alone; the K x H plans live in the static part.
 template <int WAVES, typename Model>
 __global__ __launch_bounds__(WAVES * 64) void sim_drive_kernel(mansy_env_tables T, EnvState* st, const double* __restrict__ fractions, int K, int H, int D,
                                                                double* throughput, int* best, float* best_total, int* versions, float* qoe_parts,
@@ -585,9 +768,12 @@ __global__ __launch_bounds__(WAVES * 64) void sim_drive_kernel(mansy_env_tables 
   extern __shared__ __align__(16) unsigned char drive_lds[];
   __shared__ typename Model::Shared sh;
   float* totals = (float*)drive_lds;
-  unsigned char* plans = drive_lds + sizeof(float) * K;
+  unsigned char* plans;
+  if constexpr (Model::schedules) plans = sh.plans; else plans = drive_lds + sizeof(float) * K;
   const int e = blockIdx.x, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   bool moved = false, sampled = false;        // wave 0's alone
+  int schedules = 1;                          // Model::schedules: K^H, the schedules of K levels
+  if constexpr (Model::schedules) for (int h = 0; h < H; ++h) schedules *= K;
   if (wave == 0) {
     EnvRegs s;
     load_state(s, st[e], lane);
@@ -607,53 +793,39 @@ __global__ __launch_bounds__(WAVES * 64) void sim_drive_kernel(mansy_env_tables 
     v.cur_idx = __builtin_amdgcn_readfirstlane(v.cur_idx); v.has_prev = __builtin_amdgcn_readfirstlane(v.has_prev);
     const int steps = steps_ahead(T, v.next_chunk, v.end_chunk, H);          // 0: a closed record, nothing to plan
     const double thr = sh.throughput;
-    const double per_chunk = thr * (double)T.chunk_length;
-    // the candidate with the largest budget leads: one wave per chunk records its rounds, the others go on from the rounds they share
-    int lead_k = 0;
-    double lead = per_chunk * fractions[0];
-    for (int k = 1; k < K; ++k) {
-      const double budget = per_chunk * fractions[k];
-      if (__ballot(budget > lead) != 0ull) { lead = budget; lead_k = k; }
-    }
-    for (int t = wave; t < steps; t += WAVES) {
-      const AllocTile a = alloc_tile(T, v.video, v.vp, v.next_chunk + t, nullptr, lane);
-      int ver = 0, total = a.base;
-      const int rounds = alloc_rounds(a, lead, lane, 0, ver, total, sh.rec_win[t], sh.rec_total[t]);
-      if (lane == 0) sh.rounds[t] = rounds;
-      plans[(lead_k * H + t) * NTL + lane] = (unsigned char)ver;
-    }
-    __syncthreads();
-    const int KS = K * steps;
-    for (int kt = wave; kt < KS; kt += WAVES) {
-      const int k = kt / steps, t = kt - k * steps;
-      if (k == lead_k) continue;
-      const double budget = per_chunk * fractions[k];
-      const AllocTile a = alloc_tile(T, v.video, v.vp, v.next_chunk + t, nullptr, lane);
-      int ver, total;
-      const int round = alloc_resume(a, budget, lead, lane, sh.rec_win[t], sh.rec_total[t], __builtin_amdgcn_readfirstlane(sh.rounds[t]), ver, total);
-      alloc_rounds(a, budget, lane, round, ver, total, nullptr, nullptr);
-      plans[(k * H + t) * NTL + lane] = (unsigned char)ver;
-    }
-    __syncthreads();
-    if (steps > 0) {
-      for (int k = wave; k < K; k += WAVES) {
-        const PlanBytes plan = {plans + k * H * NTL + lane};
-        float sum;
-        if constexpr (Model::client) {         // (network is a kernel argument: the whole workgroup takes the same side)
-          sum = network == NET_ESTIMATE ? look_walk<NET_ESTIMATE>(T, v, steps, plan, lane, thr, vmap, nullptr, nullptr)
-                                        : look_walk<NET_TRACE>(T, v, steps, plan, lane, 0.0, vmap, nullptr, nullptr);
-        } else {
-          sum = look_walk<NET_TRACE>(T, v, steps, plan, lane, 0.0, T.vp_gt, nullptr, nullptr);
+    int P = K;                                // the totals wave 0 scans: one per candidate, or one per schedule prefix
+    if constexpr (Model::schedules) {
+      P = sched_search<WAVES>(T, v, steps, thr, fractions, K, H, network, vmap, sh, totals, wave, lane);
+    } else {
+      drive_allocate<WAVES>(T, v, steps, thr * (double)T.chunk_length, fractions, K, H, plans, sh, wave, lane);
+      if (steps > 0) {
+        for (int k = wave; k < K; k += WAVES) {
+          const PlanBytes plan = {plans + k * H * NTL + lane};
+          float sum;
+          if constexpr (Model::client) {       // (network is a kernel argument: the whole workgroup takes the same side)
+            sum = network == NET_ESTIMATE ? look_walk<NET_ESTIMATE>(T, v, steps, plan, lane, thr, vmap, nullptr, nullptr)
+                                          : look_walk<NET_TRACE>(T, v, steps, plan, lane, 0.0, vmap, nullptr, nullptr);
+          } else {
+            sum = look_walk<NET_TRACE>(T, v, steps, plan, lane, 0.0, T.vp_gt, nullptr, nullptr);
+          }
+          if (lane == 0) totals[k] = sum;
         }
-        if (lane == 0) totals[k] = sum;
       }
+      __syncthreads();
     }
-    __syncthreads();
     if (wave == 0) {
       const size_t row = (size_t)e * D + d;
       int b = 0, ver = 0;
       float bt = 0.f;                         // a closed record: plans and totals are zeros, candidate 0
-      if (steps > 0) { b = best_of(totals, K, lane); bt = totals[b]; ver = plans[b * H * NTL + lane]; }
+      if (steps > 0) {
+        b = best_of(totals, P, lane); bt = totals[b];
+        if constexpr (Model::schedules) {      // K levels: prefix b begins with level b / K^(steps-1) and is schedule b x K^(H-steps)
+          ver = plans[b / (P / K) * H * NTL + lane];
+          b *= schedules / P;
+        } else {
+          ver = plans[b * H * NTL + lane];
+        }
+      }
       if (lane == 0) {
         if (best) best[row] = b;
         if (best_total) best_total[row] = bt;
@@ -852,6 +1024,73 @@ int mansy_sim_drive_client(const mansy_env_tables* T, void* state, int n, const 
                  throughput, best, best_total, versions, qoe_parts, scalars, over, auto_reset, network, vmap, window, history, count);
   else
     MANSY_LAUNCH((sim_drive_kernel<4, DriveClient>), dim3((unsigned)n), dim3(4 * 64), lds, (hipStream_t)stream, *T, (EnvState*)state, fractions, K, H, D,
+                 throughput, best, best_total, versions, qoe_parts, scalars, over, auto_reset, network, vmap, window, history, count);
+  MANSY_LAUNCH_CHECK();
+  return MANSY_OK;
+}
+
+// F^H where it is at most MANSY_SIM_MAX_CANDIDATES, 0 otherwise (F and H within their own limits).
+static int schedule_count(int F, int H) {
+  long long K = 1;
+  for (int h = 0; h < H; ++h) { K *= F; if (K > MANSY_SIM_MAX_CANDIDATES) return 0; }
+  return (int)K;
+}
+
+int mansy_sim_lookahead_schedules(const mansy_env_tables* T, const void* state, int n, const double* levels, int F, int H,
+                                  const double* throughput, int network, int viewport, int* level_plans, int* level_bytes, float* total,
+                                  int* steps, int* best, float* best_total, void* stream) {
+  int rc = check_sim_tables(T, "sim_lookahead_schedules"); if (rc) return rc;
+  MANSY_REQUIRE(state, "sim_lookahead_schedules: null state");
+  MANSY_REQUIRE(levels, "sim_lookahead_schedules: null levels");
+  MANSY_REQUIRE(throughput, "sim_lookahead_schedules: null throughput");
+  MANSY_REQUIRE(steps, "sim_lookahead_schedules: null steps");
+  MANSY_REQUIRE(n >= 1, "sim_lookahead_schedules: n must be >= 1");
+  MANSY_REQUIRE(F >= 1 && F <= MANSY_SIM_SCHED_MAX_LEVELS, "sim_lookahead_schedules: F must be in [1, %d]", MANSY_SIM_SCHED_MAX_LEVELS);
+  MANSY_REQUIRE(H >= 1 && H <= MANSY_SIM_MAX_HORIZON, "sim_lookahead_schedules: H must be in [1, %d]", MANSY_SIM_MAX_HORIZON);
+  const int K = schedule_count(F, H);
+  MANSY_REQUIRE(K >= 1, "sim_lookahead_schedules: F^H must be at most %d", MANSY_SIM_MAX_CANDIDATES);
+  MANSY_REQUIRE((long long)n * K < (1ll << 31), "sim_lookahead_schedules: n * F^H must be below 2^31");
+  MANSY_REQUIRE(network == MANSY_SIM_NET_TRACE || network == MANSY_SIM_NET_ESTIMATE, "sim_lookahead_schedules: network must be MANSY_SIM_NET_TRACE (0) or MANSY_SIM_NET_ESTIMATE (1)");
+  MANSY_REQUIRE(viewport == MANSY_SIM_VIEW_GT || viewport == MANSY_SIM_VIEW_PRED, "sim_lookahead_schedules: viewport must be MANSY_SIM_VIEW_GT (0) or MANSY_SIM_VIEW_PRED (1)");
+  const unsigned char* vmap = viewport == MANSY_SIM_VIEW_PRED ? T->vp_pred : T->vp_gt;
+  const size_t lds = sizeof(float) * K;                            // the totals; mansy_sim_drive's two workgroup widths
+  if (n <= DRIVE_WIDE_SESSIONS)
+    MANSY_LAUNCH(sim_lookahead_schedules_kernel<16>, dim3((unsigned)n), dim3(16 * 64), lds, (hipStream_t)stream, *T, (const EnvState*)state, levels, F, H, K,
+                 throughput, network, vmap, level_plans, level_bytes, total, steps, best, best_total);
+  else
+    MANSY_LAUNCH(sim_lookahead_schedules_kernel<4>, dim3((unsigned)n), dim3(4 * 64), lds, (hipStream_t)stream, *T, (const EnvState*)state, levels, F, H, K,
+                 throughput, network, vmap, level_plans, level_bytes, total, steps, best, best_total);
+  MANSY_LAUNCH_CHECK();
+  return MANSY_OK;
+}
+
+int mansy_sim_drive_schedules(const mansy_env_tables* T, void* state, int n, const double* levels, int F, int H, int D, double* throughput,
+                              int network, int viewport, int window, double* history, int* count, int* best, float* best_total,
+                              int* versions, float* qoe_parts, double* scalars, unsigned char* over, int auto_reset, void* stream) {
+  int rc = check_sim_tables(T, "sim_drive_schedules"); if (rc) return rc;
+  MANSY_REQUIRE(state, "sim_drive_schedules: null state");
+  MANSY_REQUIRE(levels, "sim_drive_schedules: null levels");
+  MANSY_REQUIRE(throughput, "sim_drive_schedules: null throughput");
+  MANSY_REQUIRE(history, "sim_drive_schedules: null history");
+  MANSY_REQUIRE(count, "sim_drive_schedules: null count");
+  MANSY_REQUIRE(over, "sim_drive_schedules: null over");
+  MANSY_REQUIRE(n >= 1, "sim_drive_schedules: n must be >= 1");
+  MANSY_REQUIRE(F >= 1 && F <= MANSY_SIM_SCHED_MAX_LEVELS, "sim_drive_schedules: F must be in [1, %d]", MANSY_SIM_SCHED_MAX_LEVELS);
+  MANSY_REQUIRE(H >= 1 && H <= MANSY_SIM_MAX_HORIZON, "sim_drive_schedules: H must be in [1, %d]", MANSY_SIM_MAX_HORIZON);
+  const int K = schedule_count(F, H);
+  MANSY_REQUIRE(K >= 1, "sim_drive_schedules: F^H must be at most %d", MANSY_SIM_MAX_CANDIDATES);
+  MANSY_REQUIRE((long long)n * K < (1ll << 31), "sim_drive_schedules: n * F^H must be below 2^31");
+  MANSY_REQUIRE(D >= 1 && D <= MANSY_SIM_DRIVE_MAX_DECISIONS, "sim_drive_schedules: D must be in [1, %d]", MANSY_SIM_DRIVE_MAX_DECISIONS);
+  MANSY_REQUIRE(network == MANSY_SIM_NET_TRACE || network == MANSY_SIM_NET_ESTIMATE, "sim_drive_schedules: network must be MANSY_SIM_NET_TRACE (0) or MANSY_SIM_NET_ESTIMATE (1)");
+  MANSY_REQUIRE(viewport == MANSY_SIM_VIEW_GT || viewport == MANSY_SIM_VIEW_PRED, "sim_drive_schedules: viewport must be MANSY_SIM_VIEW_GT (0) or MANSY_SIM_VIEW_PRED (1)");
+  MANSY_REQUIRE(window >= 1 && window <= MANSY_SIM_EST_MAX_WINDOW, "sim_drive_schedules: window must be in [1, %d]", MANSY_SIM_EST_MAX_WINDOW);
+  const unsigned char* vmap = viewport == MANSY_SIM_VIEW_PRED ? T->vp_pred : T->vp_gt;
+  const size_t lds = sizeof(float) * K;                            // the totals of the schedules; the kernel's K is the number of levels
+  if (n <= DRIVE_WIDE_SESSIONS)
+    MANSY_LAUNCH((sim_drive_kernel<16, DriveSchedules>), dim3((unsigned)n), dim3(16 * 64), lds, (hipStream_t)stream, *T, (EnvState*)state, levels, F, H, D,
+                 throughput, best, best_total, versions, qoe_parts, scalars, over, auto_reset, network, vmap, window, history, count);
+  else
+    MANSY_LAUNCH((sim_drive_kernel<4, DriveSchedules>), dim3((unsigned)n), dim3(4 * 64), lds, (hipStream_t)stream, *T, (EnvState*)state, levels, F, H, D,
                  throughput, best, best_total, versions, qoe_parts, scalars, over, auto_reset, network, vmap, window, history, count);
   MANSY_LAUNCH_CHECK();
   return MANSY_OK;
