@@ -348,6 +348,33 @@ def mtio_mix(history, current, future, num_head, repeat, perms):
     return torch.cat(hs, -1), torch.cat(cs, -1), torch.cat(fs, -1)
 
 
+def trainable_keys(sd):
+    """The state-dict entries the engine trains: floating, not a BatchNorm running statistic, not the positional table."""
+    return [k for k, v in sd.items() if v.dtype.is_floating_point and 'running_' not in k and k != 'positional_embedding.pe']
+
+
+def grads_autograd(sd, src, cur, gt, T, dropout_seed, p_pe, p_drop, dtype=torch.float64):
+    """One train-mode forward + MTIO loss + backward of the oracle with every floating entry of `sd` and the inputs cast to
+    `dtype` (the arithmetic above is dtype-agnostic: nothing in it names float32 except the 0/1 dropout mask, which promotes).
+    The values stay the fp32 numbers, so in float64 this is the exact function of the engine's own parameters.  `dropout_seed`
+    None = dropout off.  src [B,S,6], cur [B,1,6], gt [B,T,6] are the already-mixed MTIO tensors (mtio_mix).
+    -> (pred, loss, {name: grad}, last_bn_stats), all detached and in `dtype`."""
+    full = {k: (v.detach().to(dtype) if v.dtype.is_floating_point else v) for k, v in sd.items()}
+    params = {k: full[k].clone().requires_grad_(True) for k in trainable_keys(sd)}
+    full.update(params)
+    orc = VPOracle(full, fut_window=T, p_pe=p_pe, p_drop=p_drop)
+    pred = orc.process_src_current(src.to(dtype), cur.to(dtype), train=True, dropout_seed=dropout_seed)
+    loss = orc.loss_function(pred, gt.to(dtype))
+    loss.backward()
+    grads = {k: p.grad.detach() for k, p in params.items()}
+    return pred.detach(), loss.detach(), grads, tuple(t.detach() for t in orc.last_bn_stats)
+
+
+def grads_fp64(sd, src, cur, gt, T, dropout_seed, p_pe, p_drop):
+    """grads_autograd in float64: the independent answer for gradients with dropout ON (tests/test_gpu_vp_dropout_grads.py)."""
+    return grads_autograd(sd, src, cur, gt, T, dropout_seed, p_pe, p_drop, dtype=torch.float64)
+
+
 def adamw_step(p, g, m, v, step, lr=1e-4, b1=0.9, b2=0.999, eps=1e-8, wd=0.01):
     """torch.optim.AdamW single-tensor math (run_models.py:29 uses torch defaults)."""
     p = p * (1 - lr * wd)

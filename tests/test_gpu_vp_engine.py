@@ -2,7 +2,9 @@
   * against golden vectors produced by the imported reference (tests/golden/vp_*.npz): eval forward,
     sample(), train forward (both MTIO branches), loss, every gradient, BN running stats, one AdamW step;
   * against the oracle (oracle/vp_oracle.py) on every named intermediate, with dropout OFF and with dropout
-    ON through the shared counter hash;
+    ON through the shared counter hash -- FORWARD activations only: every gradient check in this file runs with
+    dropout off; gradients with dropout ON (the masks the backward redraws) meet a float64 answer in
+    tests/test_gpu_vp_dropout_grads.py;
   * size-independent properties at the bench size (B=4096).
 fp32 tolerance from north_star: 1e-4 on outputs (observed ~1e-6)."""
 import glob
